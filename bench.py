@@ -14,12 +14,21 @@ gradient_accumulation 1, synthetic SD-shaped weights and inputs (no checkpoints 
 on the boxes).  Data-parallel weak scaling: every rank runs its own micro-batch, the flat
 mapper-gradient bucket is all-reduced over RCCL; `value` = micro-steps completed by all ranks / s.
 
-Rank 0 prints ONE JSON line with the metric plus
+Rank 0 prints ONE JSON line with the metric (`value`, `ms_per_step`, ...).  A plain run does only that: set-up,
+warm-up, the timed steps, the line.  `--full` adds everything else the benchmark measures, after the timed region:
   "roofline":     measured-with-HIP-events average duration of the dominant kernel family
-                  (the MFMA implicit-GEMM conv/linear kernel) vs the fp16 dense MFMA peak
+                  (the MFMA implicit-GEMM conv/linear kernel) vs the fp16 dense MFMA peak, and every
+                  launch class of the step against its bound
   "cpu_baseline": the CPU oracle (oracle/sd_ref.py, a plain-torch fp32 restatement of the same
                   graph — diffusers itself is not installable here) timed on the host cores on a
                   bounded sample.  Reported, non-target.
+  config extras:  the VAE-moment-cache rate, Coach.train's end-to-end rate and the inference seconds per
+                  image (headline size only), and whether every rank replayed rank 0's tile picks (N > 1).
+`--dump-outputs DIR` writes what the last timed step computed (loss, mapper parameters and gradients, the UNet's
+prediction) as DIR/<name>.npy.  The inputs are seeded and the headline workload replays the committed GEMM tile picks
+(bench_picks.json), so every run with the same arguments computes the same bits (the loss, whose block sums are added
+atomically, to rounding) and two builds can be compared output for output.  Other sizes tune the problems the picks do
+not cover; runs that share one picks file (VNETI_AUTOTUNE_CACHE=<path>, written by the first) agree there too.
 """
 from __future__ import annotations
 
@@ -49,6 +58,8 @@ TILE_NAMES = {1: "gemm_kernel<128,128,64,64>", 2: "gemm_kernel<128,64,64,32>", 3
 # algorithmic FLOPs per sample at 512^2, SD-1.5: VAE 1116.7 + CLIP 16x13.3 + UNet fwd 803.3
 # + UNet dgrad 929.4 + CLIP dgrad 216 GF
 ALGO_GFLOP_PER_SAMPLE_512 = 3278.0
+# the autotuner's tile picks for the headline workload on an MI355X, per precision (engine/schedule.py autotune() format)
+PICKS = os.path.join(ROOT, "bench_picks.json")
 
 
 def build_engine(args, rank, world, moment_cache: bool = False):
@@ -341,6 +352,21 @@ def moment_cache_extra(args, steps: int):
     return v
 
 
+def dump_outputs(eng, out_dir: str, loss: float):
+    """What the last timed step computed, as a caller of the train step receives it: the loss, the mapper parameters
+    after the optimizer step, their gradients and the UNet's prediction (B, h, w, C); float64 / float32 .npy files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": np.array([loss], dtype=np.float64),
+              "mapper_params": eng.params.float(),
+              "mapper_grads": eng.grads.float(),
+              "unet_pred": eng.unet.pred.float().reshape(eng.B, eng.h, eng.w, -1)}
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.cpu().contiguous().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def self_launch(n: int) -> int:
     """`python bench.py --gpus N` without a launcher: re-run this command line as N ranks of one node, one per GPU,
     under torch.distributed.run (rendezvous on 127.0.0.1, a free port); rank 0's JSON line passes straight through."""
@@ -369,11 +395,18 @@ def main():
     ap.add_argument("--cpu-steps", type=int, default=3, help="timed oracle steps of the cpu_baseline leg (after 1 warm-up)")
     ap.add_argument("--cpu-batch", type=int, default=1, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline, the CPU baseline and the config extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the per-tile GEMM replay (counter-collection runs)")
-    ap.add_argument("--no-extras", action="store_true", help="skip config.coach_steps_per_s / config.infer_s_per_image_cfg5")
+    ap.add_argument("--no-roofline", action="store_true",
+                    help="with --full: skip the per-tile GEMM replay and everything after it (counter-collection runs)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip config.coach_steps_per_s / config.infer_s_per_image_cfg5")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline(args)))
         return
@@ -399,11 +432,18 @@ def main():
         else:
             dist.init_process_group(backend)
 
-    # this run's autotuner picks, kept for the extras' subprocesses (same problems, no second tuning pass)
+    # the GEMM tile picks: a pick decides the rounding of its GEMM, which the training steps amplify, so a run that tuned
+    # its own picks computed other bits than the last.  The committed picks of this workload (PICKS) seed this run's
+    # picks file; only problems they do not cover are tuned.  The file is kept for the extras' subprocesses.
     tune_cache = None
-    if world == 1 and "VNETI_AUTOTUNE_CACHE" not in os.environ:
+    if "VNETI_AUTOTUNE_CACHE" not in os.environ:
         import tempfile
+        from view_neti_amd import lib as _lib
         tune_cache = os.path.join(tempfile.gettempdir(), f"vneti_bench_picks_{os.getpid()}.json")
+        with open(PICKS) as fh:
+            pinned = json.load(fh).get(_lib.precision(), {})
+        with open(tune_cache, "w") as fh:
+            json.dump(pinned, fh)
         os.environ["VNETI_AUTOTUNE_CACHE"] = tune_cache
     if world > 1 and backend == "nccl" and not args.no_graph:
         # N GPUs = the one-GPU graph + ONE collective node; a rank that silently fell back to [graph A -> host all-reduce ->
@@ -450,9 +490,11 @@ def main():
         rank_dts = [float(t.item()) for t in tall]
         dt = max(rank_dts)  # the contract's MAX over ranks
     loss = eng.loss()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, loss)
     # after the timed region: did every rank replay ONE schedule (rank 0's autotuner picks, parallel.shared_picks)?
     picks_equal = None
-    if dist is not None:
+    if args.full and dist is not None:
         import hashlib
         from view_neti_amd import ops as _ops
         picks = [(f.keywords.get("tile_hint"), f.keywords.get("split_k"), (f.keywords.get("conv") or {}).get("korder"))
@@ -463,7 +505,7 @@ def main():
         picks_equal = all(d_ == every[0] for d_ in every)
     cache_value = None  # measured after the headline engine is released (moment_cache_extra)
 
-    if rank == 0 and args.no_roofline:
+    if rank == 0 and args.full and args.no_roofline:
         print(json.dumps({"value": world * args.steps / dt, "unit": "steps/s", "note": "roofline pass skipped"}))
     elif rank == 0:
         from view_neti_amd import lib as _lib
@@ -471,9 +513,6 @@ def main():
         prec_short = "bf16" if prec == "bf16" else "f16"
         ms = dt / args.steps * 1e3
         value = world * args.steps / dt
-        rf = roofline_pass(eng)
-        dom = max(rf, key=lambda k: rf[k]["total_ms"])
-        d = rf[dom]
         out = {
             "metric": ("TI train steps/sec (SD-1.5 512^2 bs=4 per GPU)"
                        if (args.model, args.resolution, args.batch) == ("sd15", 512, 4) else
@@ -503,49 +542,53 @@ def main():
                        "vae_moment_cache_note": "labelled extra, NOT the metric: data.cache_vae_moments (deterministic dataset, "
                                                 "augmentation_key 0) replays the step without the VAE encoder; the headline "
                                                 "`value` runs the encoder in every timed step"},
-            "roofline": {"kernel": TILE_NAMES[dom], "bound": "mfma", "achieved": d["tflops"], "peak": MFMA_PEAK_TFLOPS,
-                         "unit": "TFLOP/s", "frac": d["tflops"] / MFMA_PEAK_TFLOPS,
-                         **pmc_traffic(TILE_NAMES[dom]),
-                         "launches_per_step": d["n"], "avg_launch_us": d["avg_us"],
-                         "algorithmic_gflop_per_launch": d["flops_per_launch"] / 1e9,
-                         "algorithmic_bytes_per_launch": d["bytes_per_launch"],
-                         "algorithmic_bytes_note": "mean over this tile's launches of A (image for implicit convs) + weights "
-                                                   "+ output + fused epilogue operands, each once; compare with `traffic`",
-                         "frac_of_true_bound": d["frac_of_bound"],
-                         "frac_of_true_bound_note": "sum over this tile's launches of max(FLOP / 2.5 PF, algorithmic bytes / 8 TB/s) "
-                                                    "divided by the measured time: launches below the ridge are rated against HBM",
-                         "all_gemm_tiles": {TILE_NAMES[k]: {"launches": v["n"], "ms_per_step": v["total_ms"],
-                                                            "tflops": v["tflops"], "frac_of_bound": v["frac_of_bound"],
-                                                            "hbm_bound_launches": v["hbm_bound_launches"]}
-                                            for k, v in rf.items()}},
         }
-        # every launch class of the step against ITS bound ("each kernel >= 60 %"), from this very run: one
-        # pass over the eager schedule with an event pair around every launch (view_neti_amd/roofline.py)
-        try:
-            from view_neti_amd.roofline import time_classes
-            cls = time_classes(eng.launches())
-            out["roofline"]["classes"] = {
-                k: {kk: (round(vv, 4) if isinstance(vv, float) else vv) for kk, vv in v.items()
-                    if kk in ("launches", "ms_per_step", "bound", "achieved", "peak", "unit", "frac", "frac_of_cobound",
-                              "cobound_frac_of_peak")}
-                for k, v in sorted(cls.items(), key=lambda kv: -kv[1]["ms_per_step"])}
-            out["roofline"]["classes_note"] = ("eager replay in schedule order, HIP events per launch, algorithmic FLOPs / bytes "
-                                               "per class; attention also against the builder's MFMA+VALU co-bound at 2.4 GHz")
-        except Exception as err:  # noqa: BLE001 (reported, never fatal for the metric)
-            out["roofline"]["classes"] = None
-            out["roofline"]["classes_error"] = f"{type(err).__name__}: {str(err)[:200]}"
-        headline = (args.model, args.resolution, args.batch) == ("sd15", 512, 4)
-        if world == 1 and (not args.no_cpu_baseline or (headline and not args.no_extras)):
-            del eng
-            torch.cuda.empty_cache()
-        if world == 1 and headline and not args.no_extras and not args.no_cpu_baseline:
+        if args.full:
+            rf = roofline_pass(eng)
+            dom = max(rf, key=lambda k: rf[k]["total_ms"])
+            d = rf[dom]
+            out["roofline"] = {"kernel": TILE_NAMES[dom], "bound": "mfma", "achieved": d["tflops"], "peak": MFMA_PEAK_TFLOPS,
+                               "unit": "TFLOP/s", "frac": d["tflops"] / MFMA_PEAK_TFLOPS,
+                               **pmc_traffic(TILE_NAMES[dom]),
+                               "launches_per_step": d["n"], "avg_launch_us": d["avg_us"],
+                               "algorithmic_gflop_per_launch": d["flops_per_launch"] / 1e9,
+                               "algorithmic_bytes_per_launch": d["bytes_per_launch"],
+                               "algorithmic_bytes_note": "mean over this tile's launches of A (image for implicit convs) + weights "
+                                                         "+ output + fused epilogue operands, each once; compare with `traffic`",
+                               "frac_of_true_bound": d["frac_of_bound"],
+                               "frac_of_true_bound_note": "sum over this tile's launches of max(FLOP / 2.5 PF, algorithmic bytes / 8 TB/s) "
+                                                          "divided by the measured time: launches below the ridge are rated against HBM",
+                               "all_gemm_tiles": {TILE_NAMES[k]: {"launches": v["n"], "ms_per_step": v["total_ms"],
+                                                                  "tflops": v["tflops"], "frac_of_bound": v["frac_of_bound"],
+                                                                  "hbm_bound_launches": v["hbm_bound_launches"]}
+                                                  for k, v in rf.items()}}
+            # every launch class of the step against ITS bound ("each kernel >= 60 %"), from this very run: one
+            # pass over the eager schedule with an event pair around every launch (view_neti_amd/roofline.py)
             try:
-                out["config"]["steps_per_s_with_vae_moment_cache"] = moment_cache_extra(args, args.steps)
-            except Exception as err:  # noqa: BLE001
-                out["config"]["steps_per_s_with_vae_moment_cache_error"] = f"{type(err).__name__}: {str(err)[:200]}"
-            out["config"].update(driver_timed_extras(tune_cache or os.environ.get("VNETI_AUTOTUNE_CACHE")))
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline_bounded(args)
+                from view_neti_amd.roofline import time_classes
+                cls = time_classes(eng.launches())
+                out["roofline"]["classes"] = {
+                    k: {kk: (round(vv, 4) if isinstance(vv, float) else vv) for kk, vv in v.items()
+                        if kk in ("launches", "ms_per_step", "bound", "achieved", "peak", "unit", "frac", "frac_of_cobound",
+                                  "cobound_frac_of_peak")}
+                    for k, v in sorted(cls.items(), key=lambda kv: -kv[1]["ms_per_step"])}
+                out["roofline"]["classes_note"] = ("eager replay in schedule order, HIP events per launch, algorithmic FLOPs / bytes "
+                                                   "per class; attention also against the builder's MFMA+VALU co-bound at 2.4 GHz")
+            except Exception as err:  # noqa: BLE001 (reported, never fatal for the metric)
+                out["roofline"]["classes"] = None
+                out["roofline"]["classes_error"] = f"{type(err).__name__}: {str(err)[:200]}"
+            headline = (args.model, args.resolution, args.batch) == ("sd15", 512, 4)
+            if world == 1 and (not args.no_cpu_baseline or (headline and not args.no_extras)):
+                del eng
+                torch.cuda.empty_cache()
+            if world == 1 and headline and not args.no_extras and not args.no_cpu_baseline:
+                try:
+                    out["config"]["steps_per_s_with_vae_moment_cache"] = moment_cache_extra(args, args.steps)
+                except Exception as err:  # noqa: BLE001
+                    out["config"]["steps_per_s_with_vae_moment_cache_error"] = f"{type(err).__name__}: {str(err)[:200]}"
+                out["config"].update(driver_timed_extras(tune_cache or os.environ.get("VNETI_AUTOTUNE_CACHE")))
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline_bounded(args)
         print(json.dumps(out))
     if tune_cache:
         try:
