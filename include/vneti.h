@@ -386,6 +386,16 @@ int vneti_mapper_fwd(const float* params, const int* slot, long long slot_stride
                      const float* hidden_mask, float norm_scale, float* word, float* bypass,
                      float* save, int R, int enc_dim, int hidden, int D, int has_bypass, const float* enc_in,
                      void* stream);
+/* Per-sample object mapper (inference only, no backward): as vneti_mapper_fwd, but row r = l*Bn + b (the layout of
+ * vneti_mapper_inputs) uses the mapper at params + slots[b]*slot_stride, slots a device int32[Bn], R = nl*Bn.  The
+ * reference runs one object per text-encoder forward and asserts it (models/net_clip_text_embedding.py:65-70); each
+ * sample here gets exactly what that forward computes for its prompt alone, so prompts about different objects
+ * (training/validate.py:317-386 `infer_disentangled_objects_dtu`, the mode-3 evaluation objects) share a batch.
+ * 16-byte weight loads need slot_stride % 4 == 0, as for vneti_mapper_fwd. */
+int vneti_mapper_fwd_slots(const float* params, const int* slots, long long slot_stride, int Bn, const float* data,
+                           int nfeat, const float* w_enc, const float* hidden_mask, float norm_scale, float* word,
+                           float* bypass, float* save, int R, int enc_dim, int hidden, int D, int has_bypass,
+                           const float* enc_in, void* stream);
 /* enc_in (optional, f32 [R][enc_dim]): the first layer's input is given instead of being the Fourier encoding of
  * `data` (then data / w_enc may be NULL) — the legacy mapper of arch_view_net <= 14, whose first-layer input is the
  * output of its trainable input_layer (vneti_mapper_legacy_input_fwd below). */
@@ -410,6 +420,11 @@ long long vneti_mapper_legacy_input_params(int enc_dim, int pe_dim);
 int vneti_mapper_legacy_input_fwd(const float* params_in, const int* slot, long long slot_stride,
                                   const void* timesteps_i64, const float* w_pe, float* enc_out, int nl, int Bn,
                                   int enc_dim, int pe_dim, void* stream);
+/* per-sample form of the above (row r = l*Bn + b reads the input_layer at params_in + slots[b]*slot_stride), for
+ * vneti_mapper_fwd_slots; inference only (models/net_clip_text_embedding.py:65-70 per prompt). */
+int vneti_mapper_legacy_input_fwd_slots(const float* params_in, const int* slots, long long slot_stride,
+                                        const void* timesteps_i64, const float* w_pe, float* enc_out, int nl, int Bn,
+                                        int enc_dim, int pe_dim, void* stream);
 int vneti_mapper_legacy_input_bwd(const void* timesteps_i64, const float* w_pe, const float* denc, float* grads_in,
                                   const int* slot, long long slot_stride, int accumulate, int nl, int Bn, int enc_dim,
                                   int pe_dim, void* stream);

@@ -1,5 +1,13 @@
-"""Generate images with the mappers of a finished run (cf. the reference's scripts/inference.py /
-training/inference_dtu.py; minimal: prompts x seeds -> PNG files).
+"""Generate images with the mappers of a run.  Two command lines:
+
+  * the reference's DTU novel-view evaluation (its scripts/inference.py contract, `InferenceConfig`): every evaluation
+    view x seed (x evaluation object in mode 3), batched (`batch` prompts per sampler run), written to
+    `inference_dir` as preds_object_{tok}_iter_{it}_seed{s}.png and results_all_iter_{it}_scans_{toks}_seeds_{seeds}.pt
+
+    python scripts/inference.py --config_path input_configs/inference.yaml --input_dir <run> --iteration 1500 \
+        [--seeds [0,1]] [--batch 8]
+
+  * free prompts x seeds -> PNG files:
 
     python scripts/inference.py --exp_dir results/train --prompt "<view_dtu12d_cam22_…>. A photo of a <object>" \
         --seeds 0 1 --steps 30 --guidance 7.5 --out out/
@@ -15,7 +23,19 @@ from view_neti_amd.compat.inference import load_inference  # noqa: E402
 from view_neti_amd.compat.sd_pipeline_call import sd_pipeline_call  # noqa: E402
 
 
+REFERENCE_KEYS = ("--config_path", "--input_dir", "--iteration")
+
+
+def main_reference(args):
+    from view_neti_amd.compat.inference_dtu import parse_inference_config, run
+    results = run(parse_inference_config(args))
+    for key, res in results.items():
+        print(key, {k: round(v, 5) for k, v in res.items() if k.endswith("_mean")})
+
+
 def main():
+    if any(a.split("=")[0] in REFERENCE_KEYS for a in sys.argv[1:]):
+        return main_reference(sys.argv[1:])
     ap = argparse.ArgumentParser()
     ap.add_argument("--exp_dir", required=True)
     ap.add_argument("--mapper", default="mapper-final")

@@ -6,7 +6,11 @@
                        (what the reference's PromptManager.embed_prompt returns, prompt_manager.py:79-99), one dict, or one
                        (B, 77, D) tensor — fed straight to the UNet's per-layer K / V sources, the engine's text pass skipped;
                        OR the light `PromptEmbeds` record of this package's PromptManager (conditioning computed inside
-                       the loop, 16 layers per launch schedule)
+                       the loop, 16 layers per launch schedule), OR a list of B such records: one prompt per sample of the
+                       batch (different views / objects; an engine built with per_sample_slots maps each sample's object
+                       token to its mapper through `pipeline.object_slot`)
+    generator       -> one torch.Generator, or a list of B (diffusers' prepare_latents): sample i is then
+                       randn((1, 4, h, w), generator[i]), the draw a B = 1 call with that generator makes
     height / width  -> fixed at engine construction; passing different values raises
     scheduler       -> `pipeline.sampler` ("dpm++2m" as installed by validate.py:568, or "ddim")
 Returns an object with `.images` (list of PIL images, `output_type="pil"`) or the array, like the reference.
@@ -28,6 +32,7 @@ class InferencePipeline:
     engine: InferenceEngine
     tokenizer: Any
     sampler: str = "dpm++2m"
+    object_slot: Optional[Dict[int, int]] = None  # object token id -> mapper slot of the engine's bucket (per-sample prompts)
 
 
 @dataclass
@@ -45,12 +50,31 @@ def get_neg_prompt_input_ids(pipeline: InferencePipeline, negative_prompt: Optio
                               truncation=True, return_tensors="pt")
 
 
+def set_prompt_list(pipeline: InferencePipeline, prompts: List[PromptEmbeds]) -> None:
+    """B PromptEmbeds -> InferenceEngine.set_prompts (ids, placeholders, camera parameters, object slot per sample)"""
+    eng = pipeline.engine
+    if len(prompts) != eng.B:
+        raise ValueError(f"{len(prompts)} prompts for an engine built for batch {eng.B}")
+    ids = torch.cat([p.input_ids.reshape(1, -1) for p in prompts])
+    po = torch.cat([p.input_ids_placeholder_object.reshape(1) for p in prompts])
+    pv = torch.cat([p.input_ids_placeholder_view.reshape(1) for p in prompts])
+    with_view = [p.view_params is not None for p in prompts]
+    vp = torch.cat([p.view_params.reshape(1, -1) for p in prompts]) if all(with_view) else None
+    if any(with_view) and vp is None:
+        raise ValueError("either every prompt of the batch holds a view token or none does")
+    slots = None
+    if eng.slots is not None:
+        table = pipeline.object_slot or {}
+        slots = [table.get(int(t), 0) for t in po]
+    eng.set_prompts(ids, po, pv, vp, slots, [p.truncation_idx for p in prompts])
+
+
 @torch.no_grad()
 def sd_pipeline_call(pipeline: InferencePipeline, prompt_embeds: Union[PromptEmbeds, List[Dict[str, Any]], Dict[str, Any],
                                                                        torch.Tensor], height: Optional[int] = None,
                      width: Optional[int] = None, num_inference_steps: int = 50, guidance_scale: float = 7.5,
                      negative_prompt: Optional[Union[str, List[str]]] = None, num_images_per_prompt: Optional[int] = 1,
-                     eta: float = 0.0, generator: Optional[torch.Generator] = None,
+                     eta: float = 0.0, generator: Optional[Union[torch.Generator, List[torch.Generator]]] = None,
                      latents: Optional[torch.Tensor] = None, output_type: Optional[str] = "pil",
                      return_dict: bool = True):
     eng = pipeline.engine
@@ -65,8 +89,19 @@ def sd_pipeline_call(pipeline: InferencePipeline, prompt_embeds: Union[PromptEmb
     neg = get_neg_prompt_input_ids(pipeline, negative_prompt)
     eng.set_negative_prompt(neg.input_ids)
     if latents is None:  # pipeline.prepare_latents: randn(shape, generator) * init_noise_sigma (= 1)
-        latents = torch.randn((B, eng.Lc, eng.h, eng.w), generator=generator, dtype=torch.float32)
-    if isinstance(prompt_embeds, PromptEmbeds):
+        if isinstance(generator, list):
+            if len(generator) != B:
+                raise ValueError(f"{len(generator)} generators for a batch of {B}")
+            latents = torch.cat([torch.randn((1, eng.Lc, eng.h, eng.w), generator=g, dtype=torch.float32)
+                                 for g in generator])
+        else:
+            latents = torch.randn((B, eng.Lc, eng.h, eng.w), generator=generator, dtype=torch.float32)
+    if isinstance(prompt_embeds, list) and prompt_embeds and all(isinstance(p, PromptEmbeds) for p in prompt_embeds):
+        # one prompt per sample (distinct from the reference's list of per-step dicts: dispatch on the element type)
+        set_prompt_list(pipeline, prompt_embeds)
+        out = eng.generate(latents.to(eng.dev), num_inference_steps, guidance_scale, pipeline.sampler,
+                           decode=output_type != "latent")
+    elif isinstance(prompt_embeds, PromptEmbeds):
         rep = lambda t: None if t is None else t.expand(B, *t.shape[1:]) if t.dim() > 1 else t.expand(B)
         eng.set_prompt(rep(prompt_embeds.input_ids), rep(prompt_embeds.input_ids_placeholder_object),
                        rep(prompt_embeds.input_ids_placeholder_view), rep(prompt_embeds.view_params),

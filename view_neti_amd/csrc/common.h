@@ -63,6 +63,17 @@ int vneti_check_launch(const char* what);
     }                                         \
   } while (0)
 
+// Outputs stored through a buffer resource (vn_st16_wt and the split-K workspace) have a range of 0x7fffffff bytes: a store
+// past it is dropped without a fault.  Launchers compute the addressed extent, ((rows - 1) * ld + cols) * elem_bytes plus
+// (batch - 1) * batch_stride elements, and refuse anything at or over the range before any HIP call.
+inline long long vn_out_bytes(long long rows, long long ld, long long cols, long long elem_bytes, long long batch = 1,
+                              long long batch_stride = 0) {
+  return ((batch - 1) * batch_stride + (rows - 1) * ld + cols) * elem_bytes;
+}
+#define VN_REQUIRE_OUT(what, bytes)                                                                              \
+  VN_REQUIRE((bytes) < 0x7fffffffLL, "%s: output spans %lld bytes, over the 2 GiB range of the buffer stores", what, \
+             (long long)(bytes))
+
 // An offset guaranteed to be out of range for any buffer resource we build
 // (all tensors are < 2 GiB): raw buffer loads at this offset return zeros.
 #define VN_OOB 0x80000000u

@@ -152,6 +152,7 @@ extern "C" int vneti_conv3x3_in(const void* x, int x_is_f32, long long sb, long 
   VN_REQUIRE(C >= 1 && C <= 3, "conv3x3_in: C=%d (9*C must fit one 32-wide k-step)", C);
   VN_REQUIRE(Co > 0 && Co % 128 == 0, "conv3x3_in: Co=%d must be a multiple of 128", Co);
   VN_REQUIRE(Bn > 0 && H > 0 && W > 0 && ldo % 8 == 0, "conv3x3_in: bad geometry");
+  VN_REQUIRE_OUT("conv3x3_in", vn_out_bytes((long long)Bn * H * W, ldo, Co, 2));
   ConvInArgs a;
   a.x = x;
   a.sb = sb;

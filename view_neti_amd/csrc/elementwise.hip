@@ -455,6 +455,7 @@ extern "C" int vneti_add_f16(const void* a, long long lda, const void* b, long l
                              int rows, int cols, void* stream) {
   VN_REQUIRE(a && b && out && rows > 0 && cols > 0 && cols % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 && ldo % 8 == 0,
              "add_f16: bad arguments");
+  VN_REQUIRE_OUT("add_f16", vn_out_bytes(rows, ldo, cols, 2));
   long long n = (long long)rows * (cols / 8);
   hipLaunchKernelGGL(add_kernel, dim3((unsigned)cdivl(n, 256)), dim3(256), 0, ST, (const half_t*)a, lda,
                      (const half_t*)b, ldb, (half_t*)out, ldo, rows, cols / 8);
@@ -506,6 +507,7 @@ extern "C" int vneti_sum2x2_f16(const void* in, long long ldi, void* out, long l
                                 int C, void* stream) {
   VN_REQUIRE(in && out && Bn > 0 && H > 0 && W > 0 && C % 8 == 0 && ldi % 8 == 0 && ldo % 8 == 0,
              "sum2x2: bad arguments");
+  VN_REQUIRE_OUT("sum2x2", vn_out_bytes((long long)Bn * H * W, ldo, C, 2));
   long long n = (long long)Bn * H * W * (C / 8);
   hipLaunchKernelGGL(sum2x2_kernel, dim3((unsigned)cdivl(n, 256)), dim3(256), 0, ST, (const half_t*)in, ldi,
                      (half_t*)out, ldo, Bn, H, W, C / 8);

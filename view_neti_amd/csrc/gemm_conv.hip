@@ -923,6 +923,8 @@ extern "C" int vneti_gemm_f16(const vneti_gemm_desc* d, void* stream) {
   if (!d->out_f32) {
     VN_REQUIRE(d->ldc % 8 == 0 || d->N < 8, "gemm: ldc=%lld must be a multiple of 8", d->ldc);
   }
+  VN_REQUIRE_OUT("gemm C", vn_out_bytes(d->M, d->ldc, d->N, d->out_f32 ? 4 : 2, batch, d->strideC));
+  if (d->C2) VN_REQUIRE_OUT("gemm C2", vn_out_bytes(d->M, d->ldc2, d->geglu == 1 ? d->N / 2 : d->N, 2));
   hipStream_t st = (hipStream_t)stream;
   bool f32 = d->out_f32 != 0;
   VN_REQUIRE(!(f32 && d->rowadd), "gemm: rowadd is only supported for f16 output");
@@ -988,6 +990,8 @@ extern "C" int vneti_gemm_f16(const vneti_gemm_desc* d, void* stream) {
                "gemm: split_k=%d needs %lld workspace bytes", ks, (long long)ks * batch * d->M * d->N * 4);
     VN_REQUIRE(batch == 1 || (d->strideC != 0), "gemm: batched split-K needs strideC");
     VN_REQUIRE((long long)batch * d->M * ((d->N + 3) / 4) < 0x7fffffffLL, "gemm: split-K output larger than 2^31 chunks");
+    // the f32 partials, and the reduce's (uint32_t)(co * 4) byte offset into an f32 C (checked above with the batch stride)
+    VN_REQUIRE_OUT("gemm split-K workspace", (long long)ks * batch * d->M * d->N * 4);
   }
   if (cfg == 18 && ks > d->Ci / 64) ks = d->Ci / 64;  // the halo form splits in whole 64-channel chunks
   g.ksplit = ks;

@@ -840,6 +840,7 @@ extern "C" int vneti_groupnorm_fwd(const void* x, long long ldx, void* y, long l
   VN_REQUIRE(gn_geom(g, Bn, HW, C, G) == 0, "groupnorm: unsupported shape B=%d HW=%d C=%d G=%d", Bn, HW, C, G);
   VN_REQUIRE(x && y && gamma && beta && mean && rstd && ws, "groupnorm_fwd: null pointer");
   VN_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0, "groupnorm_fwd: ld must be a multiple of 8");
+  VN_REQUIRE_OUT("groupnorm_fwd", vn_out_bytes((long long)Bn * HW, ldy, C, 2));
   hipStream_t st = (hipStream_t)stream;
   if (gn_use_small(Bn, HW, C, G, false)) {
     if (silu)
@@ -875,6 +876,7 @@ extern "C" int vneti_groupnorm_fwd_sums(const void* x, long long ldx, void* y, l
   VN_REQUIRE(gn_geom(g, Bn, HW, C, G) == 0, "groupnorm: unsupported shape B=%d HW=%d C=%d G=%d", Bn, HW, C, G);
   VN_REQUIRE(x && y && gamma && beta && sums && mean && rstd && slots > 0, "groupnorm_fwd_sums: null pointer");
   VN_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0, "groupnorm_fwd_sums: ld % 8 != 0");
+  VN_REQUIRE_OUT("groupnorm_fwd_sums", vn_out_bytes((long long)Bn * HW, ldy, C, 2));
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(g.nslab, Bn);
   if (silu)
@@ -901,6 +903,7 @@ extern "C" int vneti_groupnorm_fwd_2l(const void* x, long long ldx, void* y, lon
   VN_REQUIRE(gn_geom(g, Bn, HW, C, G) == 0, "groupnorm: unsupported shape B=%d HW=%d C=%d G=%d", Bn, HW, C, G);
   VN_REQUIRE(x && y && gamma && beta && mean && rstd && sums && slots > 0, "groupnorm_fwd_2l: null pointer");
   VN_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0, "groupnorm_fwd_2l: ld must be a multiple of 8");
+  VN_REQUIRE_OUT("groupnorm_fwd_2l", vn_out_bytes((long long)Bn * HW, ldy, C, 2));
   if (gn_use_small(Bn, HW, C, G, false))
     return vneti_groupnorm_fwd(x, ldx, y, ldy, gamma, beta, mean, rstd, sums, Bn, HW, C, G, eps, silu, stream);
   hipStream_t st = (hipStream_t)stream;
@@ -923,6 +926,7 @@ extern "C" int vneti_groupnorm_bwd(const void* dy, long long lddy, const void* x
   VN_REQUIRE(gn_geom(g, Bn, HW, C, G) == 0, "groupnorm: unsupported shape B=%d HW=%d C=%d G=%d", Bn, HW, C, G);
   VN_REQUIRE(dy && x && gamma && beta && mean && rstd && dx && ws, "groupnorm_bwd: null pointer");
   VN_REQUIRE(ldx % 8 == 0 && lddy % 8 == 0 && lddx % 8 == 0 && ldacc % 8 == 0, "groupnorm_bwd: ld % 8 != 0");
+  VN_REQUIRE_OUT("groupnorm_bwd", vn_out_bytes((long long)Bn * HW, lddx, C, 2));
   hipStream_t st = (hipStream_t)stream;
   if (gn_use_small(Bn, HW, C, G, true)) {
     if (silu)
@@ -965,6 +969,7 @@ extern "C" int vneti_groupnorm_bwd_2l(const void* dy, long long lddy, const void
   VN_REQUIRE(gn_geom(g, Bn, HW, C, G) == 0, "groupnorm: unsupported shape B=%d HW=%d C=%d G=%d", Bn, HW, C, G);
   VN_REQUIRE(dy && x && gamma && beta && mean && rstd && dx && sums && slots > 0, "groupnorm_bwd_2l: null pointer");
   VN_REQUIRE(ldx % 8 == 0 && lddy % 8 == 0 && lddx % 8 == 0 && ldacc % 8 == 0, "groupnorm_bwd_2l: ld % 8 != 0");
+  VN_REQUIRE_OUT("groupnorm_bwd_2l", vn_out_bytes((long long)Bn * HW, lddx, C, 2));
   if (gn_use_small(Bn, HW, C, G, true))
     return vneti_groupnorm_bwd(dy, lddy, x, ldx, gamma, beta, mean, rstd, dx, lddx, dx_accum, ldacc, ws, Bn, HW, C, G, silu,
                                stream);
@@ -991,6 +996,7 @@ extern "C" int vneti_layernorm_fwd(const void* x, int x_is_f32, long long ldx, v
   VN_REQUIRE(x && y && gamma && beta, "layernorm_fwd: null pointer");
   VN_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && C <= 8 * 64 * LN_MAXC, "layernorm: unsupported C=%d", C);
   VN_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0, "layernorm_fwd: ld % 8 != 0");
+  VN_REQUIRE_OUT("layernorm_fwd", vn_out_bytes(rows, ldy, C, 2));
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(cdiv(rows, 4));
 #define LN_FWD(F, NCH)                                                                                        \
@@ -1024,6 +1030,8 @@ extern "C" int vneti_layernorm_bwd(const void* dy, int dy_is_f32, long long lddy
   VN_REQUIRE(ldcopy % 8 == 0, "layernorm_bwd: ldcopy % 8 != 0");
   VN_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && C <= 8 * 64 * LN_MAXC, "layernorm: unsupported C=%d", C);
   VN_REQUIRE(ldx % 8 == 0 && lddy % 8 == 0 && lddx % 8 == 0 && ldacc % 8 == 0, "layernorm_bwd: ld % 8 != 0");
+  VN_REQUIRE_OUT("layernorm_bwd", vn_out_bytes(rows, lddx, C, dx_is_f32 ? 4 : 2));
+  if (dx_f16_copy) VN_REQUIRE_OUT("layernorm_bwd f16 copy", vn_out_bytes(rows, ldcopy, C, 2));
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(cdiv(rows, 4));
   const int nc = cdiv(C / 8, 64);

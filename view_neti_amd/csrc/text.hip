@@ -151,19 +151,24 @@ __device__ void block_layernorm(float* z, const float* gamma, const float* beta,
   __syncthreads();
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(MT) void mapper_fwd_kernel(MapperParams mp, const float* __restrict__ params,
-                                                        const int* __restrict__ slot, long long slot_stride,
-                                                        const float* __restrict__ data, int nfeat,
-                                                        const float* __restrict__ w_enc,
-                                                        const float* __restrict__ hmask, float norm_scale,
-                                                        float* __restrict__ word, float* __restrict__ bypass,
-                                                        float* __restrict__ save,
-                                                        const float* __restrict__ enc_in) {
+// Slot modes of the forward bodies: SLOT_ONE = one mapper for the whole launch, params += slot[0] * slot_stride (the train
+// step and single-object inference); SLOT_PER_SAMPLE = row r = l*Bn + b (the layout of mapper_inputs_kernel) uses mapper
+// slots[b], so B prompts about different objects share one launch (inference only, no backward variant).
+enum SlotMode { SLOT_ONE = 0, SLOT_PER_SAMPLE = 1 };
+
+template <bool VEC, SlotMode SM>
+__device__ __forceinline__ void mapper_fwd_body(MapperParams mp, const float* __restrict__ params,
+                                                const int* __restrict__ slot, long long slot_stride, int Bn,
+                                                const float* __restrict__ data, int nfeat, const float* __restrict__ w_enc,
+                                                const float* __restrict__ hmask, float norm_scale,
+                                                float* __restrict__ word, float* __restrict__ bypass,
+                                                float* __restrict__ save, const float* __restrict__ enc_in) {
   __shared__ __attribute__((aligned(16))) float outs[2048 + 64], enc[MAXH], z[MAXH], xh[MAXH], y[MAXH], a[MAXH];
   __shared__ float stat[2], red[MT / 64];
   const int r = blockIdx.x, tid = threadIdx.x;
-  if (slot) params += (long long)slot[0] * slot_stride;  // which mapper of a multi-mapper bucket (device-side)
+  // which mapper of a multi-mapper bucket (device-side)
+  if constexpr (SM == SLOT_PER_SAMPLE) params += (long long)slot[r % Bn] * slot_stride;
+  else if (slot) params += (long long)slot[0] * slot_stride;
   const int E = mp.E, hd = mp.hd, D = mp.D, OD = mp.OD;
   // per-row save area: enc[E] | xh1[hd] | a1[hd] | xh2[hd] | a2m[hd] | rstd1, rstd2, wnorm, pad
   float* sv = save + (long long)r * (E + 4 * hd + 4);
@@ -213,6 +218,32 @@ __global__ __launch_bounds__(MT) void mapper_fwd_kernel(MapperParams mp, const f
     if (o < D) word[(long long)r * D + o] = outs[o] * f;
     else bypass[(long long)r * D + (o - D)] = outs[o];
   }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(MT) void mapper_fwd_kernel(MapperParams mp, const float* __restrict__ params,
+                                                        const int* __restrict__ slot, long long slot_stride,
+                                                        const float* __restrict__ data, int nfeat,
+                                                        const float* __restrict__ w_enc,
+                                                        const float* __restrict__ hmask, float norm_scale,
+                                                        float* __restrict__ word, float* __restrict__ bypass,
+                                                        float* __restrict__ save,
+                                                        const float* __restrict__ enc_in) {
+  mapper_fwd_body<VEC, SLOT_ONE>(mp, params, slot, slot_stride, 1, data, nfeat, w_enc, hmask, norm_scale, word, bypass,
+                                 save, enc_in);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(MT) void mapper_fwd_slots_kernel(MapperParams mp, const float* __restrict__ params,
+                                                              const int* __restrict__ slots, long long slot_stride, int Bn,
+                                                              const float* __restrict__ data, int nfeat,
+                                                              const float* __restrict__ w_enc,
+                                                              const float* __restrict__ hmask, float norm_scale,
+                                                              float* __restrict__ word, float* __restrict__ bypass,
+                                                              float* __restrict__ save,
+                                                              const float* __restrict__ enc_in) {
+  mapper_fwd_body<VEC, SLOT_PER_SAMPLE>(mp, params, slots, slot_stride, Bn, data, nfeat, w_enc, hmask, norm_scale, word,
+                                        bypass, save, enc_in);
 }
 
 // backward stage 1: per row, from (d_word, d_bypass) down to the pre-LayerNorm gradients.
@@ -343,6 +374,30 @@ __global__ __launch_bounds__(256) void legacy_input_fwd_kernel(const float* __re
   for (int k = tid; k < P2; k += 256) v[k] = legacy_pe(w_pe, nw, k, tt, ll, inv);
   __syncthreads();
   for (int o = wave; o < E; o += 4) {  // one wave per output: lanes stride the 2048 inputs (coalesced weight rows)
+    const float* wr = pin + (long long)o * P2;
+    float s = 0.f;
+    for (int k = lane; k < P2; k += 64) s += wr[k] * v[k];
+    s = wave_sum(s);
+    if (lane == 0) enc_out[(long long)r * E + o] = s + pin[(long long)E * P2 + o];
+  }
+}
+
+// legacy_input_fwd_kernel with mapper slots[b] for row r = l*Bn + b.  A separate body on purpose: routing the one-mapper
+// kernel through a shared inline function changed its register allocation, and the train step's ISA stays byte-identical.
+__global__ __launch_bounds__(256) void legacy_input_fwd_slots_kernel(const float* __restrict__ pin,
+                                                                     const int* __restrict__ slots, long long slot_stride,
+                                                                     const long long* __restrict__ t,
+                                                                     const float* __restrict__ w_pe,
+                                                                     float* __restrict__ enc_out, int nl, int Bn, int E,
+                                                                     int P2) {
+  __shared__ float v[4096];
+  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  pin += (long long)slots[r % Bn] * slot_stride;
+  const int nw = P2 / 2;
+  const float tt = (float)t[r % Bn], ll = (float)(r / Bn), inv = rsqrtf((float)nw);
+  for (int k = tid; k < P2; k += 256) v[k] = legacy_pe(w_pe, nw, k, tt, ll, inv);
+  __syncthreads();
+  for (int o = wave; o < E; o += 4) {
     const float* wr = pin + (long long)o * P2;
     float s = 0.f;
     for (int k = lane; k < P2; k += 64) s += wr[k] * v[k];
@@ -821,6 +876,25 @@ extern "C" int vneti_mapper_fwd(const float* params, const int* slot, long long 
   return vneti_check_launch("mapper_fwd");
 }
 
+extern "C" int vneti_mapper_fwd_slots(const float* params, const int* slots, long long slot_stride, int Bn,
+                                      const float* data, int nfeat, const float* w_enc, const float* hidden_mask,
+                                      float norm_scale, float* word, float* bypass, float* save, int R, int enc_dim,
+                                      int hidden, int D, int has_bypass, const float* enc_in, void* stream) {
+  MapperParams mp;
+  VN_REQUIRE(fill_mp(mp, enc_dim, hidden, D, has_bypass) > 0, "mapper_fwd_slots: unsupported dims E=%d hd=%d D=%d",
+             enc_dim, hidden, D);
+  VN_REQUIRE(params && slots && word && save && R > 0 && Bn > 0 && R % Bn == 0 &&
+                 (enc_in || (data && w_enc && nfeat > 0)) && (!has_bypass || bypass),
+             "mapper_fwd_slots: bad arguments (R=%d Bn=%d)", R, Bn);
+  if (mapper_vec_ok(mp, params, slot_stride))
+    hipLaunchKernelGGL(mapper_fwd_slots_kernel<true>, dim3(R), dim3(MT), 0, ST, mp, params, slots, slot_stride, Bn, data,
+                       nfeat, w_enc, hidden_mask, norm_scale, word, bypass, save, enc_in);
+  else
+    hipLaunchKernelGGL(mapper_fwd_slots_kernel<false>, dim3(R), dim3(MT), 0, ST, mp, params, slots, slot_stride, Bn, data,
+                       nfeat, w_enc, hidden_mask, norm_scale, word, bypass, save, enc_in);
+  return vneti_check_launch("mapper_fwd_slots");
+}
+
 extern "C" int vneti_mapper_bwd(const float* params, const int* slot, long long slot_stride,
                                 const float* hidden_mask, float norm_scale, const float* word,
                                 const float* dword_src, const int* dword_rows, long long ld_src,
@@ -854,6 +928,18 @@ extern "C" int vneti_mapper_legacy_input_fwd(const float* params_in, const int* 
   hipLaunchKernelGGL(legacy_input_fwd_kernel, dim3(nl * Bn), dim3(256), 0, ST, params_in, slot, slot_stride,
                      (const long long*)timesteps_i64, w_pe, enc_out, nl, Bn, enc_dim, pe_dim);
   return vneti_check_launch("mapper_legacy_input_fwd");
+}
+
+extern "C" int vneti_mapper_legacy_input_fwd_slots(const float* params_in, const int* slots, long long slot_stride,
+                                                   const void* timesteps_i64, const float* w_pe, float* enc_out, int nl,
+                                                   int Bn, int enc_dim, int pe_dim, void* stream) {
+  VN_REQUIRE(params_in && slots && timesteps_i64 && w_pe && enc_out && nl > 0 && Bn > 0,
+             "mapper_legacy_input_fwd_slots: bad arguments");
+  VN_REQUIRE(enc_dim > 0 && enc_dim <= MAXH && pe_dim > 0 && pe_dim <= 4096 && pe_dim % 2 == 0,
+             "mapper_legacy_input_fwd_slots: unsupported dims E=%d P=%d", enc_dim, pe_dim);
+  hipLaunchKernelGGL(legacy_input_fwd_slots_kernel, dim3(nl * Bn), dim3(256), 0, ST, params_in, slots, slot_stride,
+                     (const long long*)timesteps_i64, w_pe, enc_out, nl, Bn, enc_dim, pe_dim);
+  return vneti_check_launch("mapper_legacy_input_fwd_slots");
 }
 
 extern "C" int vneti_mapper_legacy_input_bwd(const void* timesteps_i64, const float* w_pe, const float* denc, float* grads_in,

@@ -65,6 +65,34 @@ def step_coefficients(kind: str, ac: torch.Tensor, timesteps: Sequence[int], i: 
     return float(cx), float(base * (1 + 0.5 / r0)), float(-0.5 * base / r0), float(al[t]), float(sg[t])
 
 
+_BUFFER_RANGE = 0x7fffffff  # bytes a buffer-resource store can address (csrc/common.h VN_REQUIRE_OUT)
+
+
+def decoder_sample_bytes(vae: sc.VAEConfig, h: int, w: int) -> int:
+    """the largest f16 activation of VAEDecoderEngine for ONE sample of latent size h x w: the resnet / upsample outputs
+    at each level (up block i runs at h * 2^i with max(its input, its output) channels) and the mid-block attention
+    scores (h w x rup(h w, 64))."""
+    boc = list(reversed(vae.block_out_channels))
+    peak = h * w * ((h * w + 63) // 64 * 64)
+    cin = boc[0]
+    for i, cout in enumerate(boc):
+        peak = max(peak, (h << i) * (w << i) * max(cin, cout))
+        if i < len(boc) - 1:  # the upsample conv writes cout channels at twice the resolution
+            peak = max(peak, (h << (i + 1)) * (w << (i + 1)) * cout)
+        cin = cout
+    return 2 * peak
+
+
+def decode_sub_batch(vae: sc.VAEConfig, h: int, w: int, batch: int) -> int:
+    """the largest divisor of `batch` whose decoder activations stay below the buffer-store range (equal sub-batches:
+    one decoder engine, no padded pass)"""
+    per = decoder_sample_bytes(vae, h, w)
+    for d in range(batch, 0, -1):
+        if batch % d == 0 and d * per < _BUFFER_RANGE:
+            return d
+    raise ValueError(f"one {8 * h}x{8 * w} sample needs {per} bytes in one decoder activation: over 2 GiB")
+
+
 class InferenceEngine:
     def __init__(self, cfg: sc.SDConfig, unet_w: Dict, vae_dec_w: Dict, clip_w: Dict, batch: int, height: int,
                  width: int, mapper_object: Dict[str, torch.Tensor], w_enc_object: torch.Tensor,
@@ -75,9 +103,12 @@ class InferenceEngine:
                  device: str = "cuda", params_object: Optional[torch.Tensor] = None,
                  params_view: Optional[torch.Tensor] = None, object_slot: Optional[torch.Tensor] = None,
                  object_slot_stride: int = 0, legacy_pe_object: Optional[torch.Tensor] = None,
-                 enc_dim_object: int = 64, output_bypass_object: bool = True, output_bypass_view: bool = True):
+                 enc_dim_object: int = 64, output_bypass_object: bool = True, output_bypass_view: bool = True,
+                 per_sample_slots: bool = False):
         """params_object / params_view: flat device buckets to ALIAS instead of copying the state dicts (validation
-        during training reads the live parameters); object_slot (+stride) picks one mapper of a multi-object bucket."""
+        during training reads the live parameters); object_slot (+stride) picks one mapper of a multi-object bucket.
+        per_sample_slots: every sample picks its own mapper of the bucket (`slots`, written by set_prompts), so B prompts
+        about different objects share one sampler graph; object_slot is then unused."""
         self.cfg = cfg
         self.B = batch
         self.dev = device
@@ -94,12 +125,15 @@ class InferenceEngine:
         self.ctx_k = torch.zeros((nl, B * L, D), dtype=lib.act_dtype(), device=device)
         self.ctx_v = torch.zeros_like(self.ctx_k)
         po = params_object if params_object is not None else flatten_mapper_state(mapper_object).to(device)
+        # device int32[B] the captured text pass reads (the per-sample form of `object_slot`)
+        self.slots = torch.zeros(B, dtype=torch.int32, device=device) if per_sample_slots else None
+        self.n_object_slots = po.numel() // object_slot_stride if object_slot_stride else 1
         mo = MapperState(po, w_enc_object.to(device).float().contiguous() if legacy_pe_object is None else None,
                          norm_scale_object, alpha_object, hidden=hidden_object, enc_dim=enc_dim_object,
                          unconstrained=unconstrained_object, slot=object_slot, slot_stride=object_slot_stride,
                          legacy_w_pe=(legacy_pe_object.to(device).float().contiguous()
                                       if legacy_pe_object is not None else None),
-                         output_bypass=output_bypass_object)
+                         output_bypass=output_bypass_object, slots=self.slots)
         mv = None
         if mapper_view is not None or params_view is not None:
             pv = params_view if params_view is not None else flatten_mapper_state(mapper_view).to(device)
@@ -111,11 +145,17 @@ class InferenceEngine:
         # masks exist from the start: set_truncation() then mutates them in place and a captured sampler graph
         # (whose launches bake the mask pointer in) honours a truncation_idx set after the capture
         self.text.ensure_masks()
-        self.decoder = VAEDecoderEngine(cfg.vae, vae_dec_w, batch, self.h, self.w, device)
+        # the decoder runs in sub-batches whose largest activation stays inside the 2 GiB range of the buffer stores
+        # (B = 8 at 768 x 768 puts 2.4 GB into the 256-channel full-resolution level); the UNet stays at 2B
+        self.decode_batch = decode_sub_batch(cfg.vae, self.h, self.w, batch)
+        self.decoder = VAEDecoderEngine(cfg.vae, vae_dec_w, self.decode_batch, self.h, self.w, device)
         shape = (batch, self.Lc, self.h, self.w)
         self.x = torch.zeros(shape, dtype=torch.float32, device=device)
         self.m_prev = torch.zeros_like(self.x)
-        self.image = self.decoder.image
+        if self.decode_batch == batch:
+            self.image = self.decoder.image
+        else:
+            self.image = torch.empty((batch,) + tuple(self.decoder.image.shape[1:]), dtype=torch.float32, device=device)
         self.step_idx = torch.zeros(1, dtype=torch.int32, device=device)
         # device tables a captured sampler step reads (row = step_idx): {alpha_t, sigma_t, cx, c0, c1}, timestep
         self.coef_table = torch.zeros((cfg.ddpm.num_train_timesteps, 5), dtype=torch.float32, device=device)
@@ -142,6 +182,36 @@ class InferenceEngine:
     def set_prompt(self, input_ids, placeholder_object, placeholder_view=None, view_params=None,
                    truncation_idx: Optional[int] = None):
         self.text.set_batch(input_ids, placeholder_object, placeholder_view, view_params)
+        self.text.set_truncation(truncation_idx)
+
+    def set_prompts(self, input_ids: torch.Tensor, placeholder_object: torch.Tensor,
+                    placeholder_view: Optional[torch.Tensor] = None, view_params: Optional[torch.Tensor] = None,
+                    slots: Optional[Sequence[int]] = None, truncation_idx: Optional[Sequence[Optional[int]]] = None):
+        """B different prompts, one per sample: input_ids (B, 77), placeholder ids (B,) (-1 = none), view_params (B, nv)
+        for the rows with a view token, slots[b] = which mapper of the object bucket sample b uses (needs
+        per_sample_slots).  The negative prompt and the guidance scale stay shared by the whole batch."""
+        B = self.B
+        ids = input_ids.reshape(B, self.L)
+        po = placeholder_object.reshape(B).cpu()
+        has_obj = po != -1
+        if bool(has_obj.any()) and not bool(has_obj.all()):
+            raise ValueError("set_prompts: either every prompt of the batch holds an object placeholder or none does")
+        if truncation_idx is not None and not isinstance(truncation_idx, int):
+            tr = list(truncation_idx)
+            if any(t != tr[0] for t in tr):
+                raise ValueError(f"set_prompts: one truncation_idx per batch (got {tr})")
+            truncation_idx = tr[0]
+        if slots is not None:
+            if self.slots is None:
+                raise ValueError("set_prompts: per-sample object slots need an engine built with per_sample_slots=True")
+            s = torch.as_tensor(list(slots), dtype=torch.int32).reshape(-1)
+            if s.numel() != B or bool((s < 0).any()) or bool((s >= self.n_object_slots).any()):
+                raise ValueError(f"set_prompts: need {B} slots in [0, {self.n_object_slots}), got {s.tolist()}")
+            self.slots.copy_(s)
+        elif self.slots is not None:
+            self.slots.zero_()
+        pv = placeholder_view.reshape(B) if placeholder_view is not None else None
+        self.text.set_batch(ids, po, pv, view_params)
         self.text.set_truncation(truncation_idx)
 
     # ------------------------------------------------------------------ the loop
@@ -190,8 +260,19 @@ class InferenceEngine:
                                      self.h * self.w, guidance_scale, a_t, s_t, cx, c0, c1, vpred)
         if not decode:
             return self.x
-        self.decoder.z_in.copy_(self.x)
-        self.decoder.forward()
+        return self.decode()
+
+    def decode(self) -> torch.Tensor:
+        """decode self.x into self.image, `decode_batch` samples per decoder pass"""
+        db = self.decode_batch
+        if db == self.B:
+            self.decoder.z_in.copy_(self.x)
+            self.decoder.forward()
+            return self.image
+        for i in range(0, self.B, db):
+            self.decoder.z_in.copy_(self.x[i:i + db])
+            self.decoder.forward()
+            self.image[i:i + db].copy_(self.decoder.image)
         return self.image
 
     # ------------------------------------------------------------------ the reference's own prompt_embeds contract
@@ -254,9 +335,7 @@ class InferenceEngine:
                                  guidance_scale, a_t, s_t, cx, c0, c1, vpred)
         if not decode:
             return self.x
-        self.decoder.z_in.copy_(self.x)
-        self.decoder.forward()
-        return self.image
+        return self.decode()
 
     def _one_step(self, guidance_scale, vpred):
         B, L = self.B, self.L

@@ -34,7 +34,7 @@ class MapperState:
     def __init__(self, params: torch.Tensor, w_enc: Optional[torch.Tensor], norm_scale: Optional[float], alpha: float,
                  hidden: int = 64, enc_dim: int = 64, unconstrained: bool = False, nested_dropout_prob: float = 0.0,
                  slot: Optional[torch.Tensor] = None, slot_stride: int = 0, legacy_w_pe: Optional[torch.Tensor] = None,
-                 output_bypass: bool = True):
+                 output_bypass: bool = True, slots: Optional[torch.Tensor] = None):
         # output_bypass False (models/neti_mapper.py:79-81,419-424): the mapper emits the word embedding only — no
         # CONTEXT_TENSOR_BYPASS, the value context equals the key context
         self.output_bypass = output_bypass
@@ -50,6 +50,8 @@ class MapperState:
         self.nested_dropout_prob = nested_dropout_prob  # 0 disables (use_nested_dropout=False)
         self.slot = slot                # device int32[1]: which mapper of the bucket (mapper_object_lookup)
         self.slot_stride = slot_stride
+        # device int32[B]: mapper of the bucket per SAMPLE (vneti_mapper_fwd_slots; inference only, replaces `slot`)
+        self.slots = slots
 
 
 def flatten_mapper_state(sd: Dict[str, torch.Tensor]) -> torch.Tensor:
@@ -99,6 +101,8 @@ class TextEngine(Schedule):
         self.ctx_k, self.ctx_v, self.dctx_k, self.dctx_v = ctx_k, ctx_v, dctx_k, dctx_v
         assert ctx_k.numel() == self.Rt * D and ctx_k.is_contiguous()
         self.mo, self.mv = mapper_object, mapper_view
+        if mapper_object.slots is not None and (need_backward or mapper_object.slots.numel() != batch):
+            raise ValueError("per-sample mapper slots are forward-only and need one slot per sample")
         self.go, self.gv = grads_object, grads_view
         self.train_view = train_view and mapper_view is not None
         # per-batch inputs (static buffers, refreshed by set_batch)
@@ -233,17 +237,31 @@ class TextEngine(Schedule):
             self.n_std_obj = ops.mapper_num_params(mo.enc_dim, mo.hidden, D, mo.output_bypass)
             self.bo["enc"] = self._buf((R, mo.enc_dim), torch.float32)
             self.bo["denc"] = self._buf((R, mo.enc_dim), torch.float32)
-            f.append(lambda: ops.mapper_legacy_input_fwd(mo.params[self.n_std_obj:], self.timesteps, mo.legacy_w_pe,
-                                                         self.bo["enc"], nl, B, mo.enc_dim, mo.pe_dim, mo.slot,
-                                                         mo.slot_stride))
-            f.append(lambda: ops.mapper_fwd(mo.params, None, None, self.hidden_mask_obj, mo.norm_scale, self.bo["word"],
-                                            self.bo["byp"], self.bo["save"], R, mo.enc_dim, mo.hidden, D, mo.output_bypass,
-                                            mo.slot, mo.slot_stride, enc_in=self.bo["enc"]))
+            if mo.slots is not None:
+                f.append(lambda: ops.mapper_legacy_input_fwd_slots(mo.params[self.n_std_obj:], mo.slots, mo.slot_stride,
+                                                                   self.timesteps, mo.legacy_w_pe, self.bo["enc"], nl, B,
+                                                                   mo.enc_dim, mo.pe_dim))
+                f.append(lambda: ops.mapper_fwd_slots(mo.params, mo.slots, mo.slot_stride, B, None, None,
+                                                      self.hidden_mask_obj, mo.norm_scale, self.bo["word"], self.bo["byp"],
+                                                      self.bo["save"], R, mo.enc_dim, mo.hidden, D, mo.output_bypass,
+                                                      enc_in=self.bo["enc"]))
+            else:
+                f.append(lambda: ops.mapper_legacy_input_fwd(mo.params[self.n_std_obj:], self.timesteps, mo.legacy_w_pe,
+                                                             self.bo["enc"], nl, B, mo.enc_dim, mo.pe_dim, mo.slot,
+                                                             mo.slot_stride))
+                f.append(lambda: ops.mapper_fwd(mo.params, None, None, self.hidden_mask_obj, mo.norm_scale,
+                                                self.bo["word"], self.bo["byp"], self.bo["save"], R, mo.enc_dim, mo.hidden,
+                                                D, mo.output_bypass, mo.slot, mo.slot_stride, enc_in=self.bo["enc"]))
         else:
             f.append(partial(ops.mapper_inputs, self.timesteps, None, self.bo["data"], nl, B))
-            f.append(lambda: ops.mapper_fwd(mo.params, self.bo["data"], mo.w_enc, self.hidden_mask_obj, mo.norm_scale,
-                                            self.bo["word"], self.bo["byp"], self.bo["save"], R, mo.enc_dim, mo.hidden,
-                                            D, mo.output_bypass, mo.slot, mo.slot_stride))
+            if mo.slots is not None:
+                f.append(lambda: ops.mapper_fwd_slots(mo.params, mo.slots, mo.slot_stride, B, self.bo["data"], mo.w_enc,
+                                                      self.hidden_mask_obj, mo.norm_scale, self.bo["word"], self.bo["byp"],
+                                                      self.bo["save"], R, mo.enc_dim, mo.hidden, D, mo.output_bypass))
+            else:
+                f.append(lambda: ops.mapper_fwd(mo.params, self.bo["data"], mo.w_enc, self.hidden_mask_obj, mo.norm_scale,
+                                                self.bo["word"], self.bo["byp"], self.bo["save"], R, mo.enc_dim, mo.hidden,
+                                                D, mo.output_bypass, mo.slot, mo.slot_stride))
         self.bv = None
         if self.mv is not None:
             mv = self.mv

@@ -352,6 +352,15 @@ def mapper_fwd(params, data, w_enc, hidden_mask, norm_scale, word, bypass, save,
             1 if has_bypass else 0, _p(enc_in), stream())
 
 
+def mapper_fwd_slots(params, slots, slot_stride, Bn, data, w_enc, hidden_mask, norm_scale, word, bypass, save, R, enc_dim,
+                     hidden, D, has_bypass, enc_in=None):
+    """mapper_fwd with mapper slots[b] (device int32[Bn]) for row r = l*Bn + b (inference only)"""
+    _l.call("mapper_fwd_slots", _p(params), _p(slots), slot_stride, Bn, _p(data),
+            data.shape[1] if data is not None else 0, _p(w_enc), _p(hidden_mask),
+            norm_scale if norm_scale is not None else -1.0, _p(word), _p(bypass), _p(save), R, enc_dim, hidden, D,
+            1 if has_bypass else 0, _p(enc_in), stream())
+
+
 def mapper_bwd(params, hidden_mask, norm_scale, word, dword_src, dword_rows, ld_src, dbypass, save, rowgrads, grads,
                accumulate, R, enc_dim, hidden, D, has_bypass, slot=None, slot_stride=0, denc=None):
     _l.call("mapper_bwd", _p(params), _p(slot), slot_stride, _p(hidden_mask), norm_scale if norm_scale is not None else -1.0, _p(word),
@@ -366,6 +375,11 @@ def mapper_legacy_input_params(enc_dim, pe_dim):
 def mapper_legacy_input_fwd(params_in, timesteps, w_pe, enc_out, nl, Bn, enc_dim, pe_dim, slot=None, slot_stride=0):
     _l.call("mapper_legacy_input_fwd", _p(params_in), _p(slot), slot_stride, _p(timesteps), _p(w_pe), _p(enc_out), nl, Bn,
             enc_dim, pe_dim, stream())
+
+
+def mapper_legacy_input_fwd_slots(params_in, slots, slot_stride, timesteps, w_pe, enc_out, nl, Bn, enc_dim, pe_dim):
+    _l.call("mapper_legacy_input_fwd_slots", _p(params_in), _p(slots), slot_stride, _p(timesteps), _p(w_pe), _p(enc_out),
+            nl, Bn, enc_dim, pe_dim, stream())
 
 
 def mapper_legacy_input_bwd(timesteps, w_pe, denc, grads_in, accumulate, nl, Bn, enc_dim, pe_dim, slot=None, slot_stride=0):
