@@ -506,6 +506,29 @@ int vneti_stream_create_cu_mask(const unsigned* mask, int nwords, void** stream)
 int vneti_stream_get_cu_mask(void* stream, unsigned* mask, int nwords);
 int vneti_stream_destroy(void* stream);
 
+/* ---- LPIPS(net="vgg", version="0.1") for the DTU novel-view metrics (lpips 0.1.4 as training/inference_dtu.py and
+   scripts/summarize_dtu.py construct it; csrc/lpips.hip).  The 13 VGG16 convolutions run through vneti_gemm_f16 (conv1_1 as
+   a plain GEMM over the K = 64 rows below, the others with conv_mode 1); these entries are the glue around them.
+     vneti_lpips_prep            f32 NCHW image in [-1, 1] (any strides, sb/sc/sy/sx in elements) -> ScalingLayer
+                                 (x - shift) / scale, then conv1_1's 3x3 im2col: out[m][tap*3 + c] f16, rows of 64 (27..63
+                                 zero), M = Bn*H*W; the zero padding is applied after the scaling
+     vneti_relu_f16              in place on n (% 8 == 0) contiguous 16-bit values (the eight untapped convolutions)
+     vneti_relu_maxpool2x2_f16   NHWC [Bn][H][W][C] pre-activation -> [Bn][H/2][W/2][C] relu(max 2x2), floor; C % 8 == 0
+     vneti_lpips_distance        per pair p of the int32 table pairs[P][2] (image indices into the feature batch `feat`,
+                                 NHWC [n_img][HW][C] PRE-activation of a tapped layer): mean over the HW pixels of
+                                 sum_c w[c] (n0_c - n1_c)^2, n = relu(f) / (|relu(f)|_2 + 1e-10); out[p] = that (accumulate
+                                 0) or out[p] + that (1).  ws: f32 scratch of vneti_lpips_ws_floats(P, C, HW) floats; two
+                                 launches, block partials finished in a fixed order (no float atomics: bit-reproducible,
+                                 independent of the pair's position).  C in {64, 128, 256, 512}; a pair outside
+                                 [0, n_img) yields NaN. */
+int vneti_lpips_prep(const float* x, long long sb, long long sc, long long sy, long long sx, void* out, int Bn, int H, int W,
+                     void* stream);
+int vneti_relu_f16(void* x, long long n, void* stream);
+int vneti_relu_maxpool2x2_f16(const void* x, void* y, int Bn, int H, int W, int C, void* stream);
+long long vneti_lpips_ws_floats(int P, int C, int HW);
+int vneti_lpips_distance(const void* feat, int n_img, const int* pairs, int P, const float* w, int C, int HW, float* ws,
+                         long long ws_floats, float* out, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,9 +13,10 @@ routines the reference calls are restated from their published algorithms becaus
 * `torchvision.transforms.Resize((300, 400), BICUBIC)` on uint8 tensors (torchvision 0.14 tensor path, no
   antialias): f32 `interpolate(mode="bicubic", align_corners=False)`, clamp to [0, 255], round, cast.
 * `torchvision.utils.make_grid(t, nrow)`: padding 2, pad value 0.
-* LPIPS(net="vgg") needs the VGG16 + linear-head weights of the `lpips` package, which are not available offline:
-  `lpips_fn_batch` raises; `do_lpips=False` (the reference's default, inference_dtu.py:481) reports zeros like the
-  reference does.
+* LPIPS(net="vgg") runs on the GPU (compat/lpips.py) from the user's torchvision VGG16 and lpips linear-head weight
+  files; nothing is bundled or downloaded, so `lpips_fn_batch` needs the callable
+  (`lpips_fn=LPIPS.from_files(vgg_path, lin_path)`) and raises without one.  `do_lpips=False` (the reference's
+  default, inference_dtu.py:481) reports zeros like the reference does.
 """
 from __future__ import annotations
 
@@ -255,9 +256,9 @@ def get_result_metrics_and_grids(cam_idxs, cam_idxs_train, imgs_pred_all_seeds, 
 
 def evaluate_dtu_predictions(lookup_camidx_to_img_pred: Dict[int, np.ndarray], train_data_dir, dtu_subset, dtu_lighting,
                              dtu_preprocess_key, seeds: Sequence[int], scan_id=None, masks_root=DTU_MASKS,
-                             do_lpips: bool = False, make_figures: bool = True) -> dict:
+                             do_lpips: bool = False, make_figures: bool = True, lpips_fn=None) -> dict:
     """The tail of ValidationHandler.infer_dtu (validate.py:123-152): predictions (camidx -> (n_seeds, H, W, 3) uint8)
-    against the scene's ground-truth views and object masks."""
+    against the scene's ground-truth views and object masks.  `lpips_fn`: the LPIPS callable used when do_lpips."""
     cam_idxs, cam_idxs_train, _ = get_cam_idxs(dtu_subset)
     assert set(lookup_camidx_to_img_pred.keys()) == set(cam_idxs)
     if scan_id is None:
@@ -266,4 +267,4 @@ def evaluate_dtu_predictions(lookup_camidx_to_img_pred: Dict[int, np.ndarray], t
     masks = get_object_masks(cam_idxs, scan_id, masks_root=masks_root)
     pred, gt_t, masks_t, _, gt_plot = process_imgs(cam_idxs, cam_idxs_train, lookup_camidx_to_img_pred, gt, masks)
     return get_result_metrics_and_grids(cam_idxs, cam_idxs_train, pred, gt_t, masks_t, gt_plot, list(seeds),
-                                        do_lpips=do_lpips, make_figures=make_figures)
+                                        do_lpips=do_lpips, lpips_fn=lpips_fn, make_figures=make_figures)

@@ -40,8 +40,17 @@ class InferenceConfig:
     num_denoising_steps: int = 30
     debug: int = 0
     batch: int = 8
+    # LPIPS(net="vgg") on the GPU from the user's weight files (compat/lpips.py); off by default, as in the reference
+    do_lpips: bool = False
+    lpips_vgg_weights: Optional[Path] = None
+    lpips_lin_weights: Optional[Path] = None
 
     def __post_init__(self):
+        if self.do_lpips and (self.lpips_vgg_weights is None or self.lpips_lin_weights is None):
+            raise ValueError("do_lpips needs --lpips_vgg_weights (torchvision vgg16-397923af.pth) and "
+                             "--lpips_lin_weights (lpips weights/v0.1/vgg.pth)")
+        if self.do_lpips and self.torch_dtype == "bf16":
+            raise ValueError("do_lpips: LPIPS runs on the fp16 library only (its bf16 quality is unmeasured)")
         if self.input_dir is not None and self.inference_dir is None:
             self.inference_dir = Path(self.input_dir) / "inference"
         if self.torch_dtype not in ("fp16", "bf16"):
@@ -168,14 +177,14 @@ def scene_of(train_cfg, object_token: Optional[str]) -> Tuple[Path, str]:
 
 
 def evaluate(train_cfg, per_cam: Dict[int, np.ndarray], seeds: Sequence[int], object_token: Optional[str],
-             make_figures: bool = True) -> dict:
-    """validate.py:123-152: masked MSE / PSNR / SSIM of the views against the scene (LPIPS needs weights this package
-    does not ship: its entries stay 0)"""
+             make_figures: bool = True, lpips_fn=None) -> dict:
+    """validate.py:123-152: masked MSE / PSNR / SSIM of the views against the scene, and LPIPS when an `lpips_fn`
+    (compat/lpips.py) is given (otherwise its entries stay 0, the reference's do_lpips=False)"""
     from .dtu_metrics import evaluate_dtu_predictions
     scene, scan_id = scene_of(train_cfg, object_token)
     return evaluate_dtu_predictions(per_cam, scene, train_cfg.data.dtu_subset, train_cfg.data.dtu_lighting,
                                     train_cfg.data.dtu_preprocess_key, seeds, scan_id=scan_id,
-                                    make_figures=make_figures)
+                                    make_figures=make_figures, do_lpips=lpips_fn is not None, lpips_fn=lpips_fn)
 
 
 def load_train_cfg(input_dir: Path, iteration: int):
@@ -227,9 +236,13 @@ def run(icfg: InferenceConfig) -> Dict[Optional[str], dict]:
     preds = generate_views(pipe, pm, objects, cam_idxs, seeds, icfg.num_denoising_steps)
     out_dir = Path(icfg.inference_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
+    lpips_fn = None
+    if icfg.do_lpips:
+        from .lpips import LPIPS
+        lpips_fn = LPIPS.from_files(icfg.lpips_vgg_weights, icfg.lpips_lin_weights)
     results = {}
     for key, obj in zip(keys, objects):
-        res = evaluate(train_cfg, preds[obj], seeds, obj if train_cfg.learnable_mode == 3 else None)
+        res = evaluate(train_cfg, preds[obj], seeds, obj if train_cfg.learnable_mode == 3 else None, lpips_fn=lpips_fn)
         for i, grid in enumerate(res["grids"]):
             name = out_dir / preds_png_name(key, icfg.iteration, seeds[i])
             if res["figures"]:

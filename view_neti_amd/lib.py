@@ -236,6 +236,10 @@ SIGNATURES = {
     "stream_create_cu_mask": [C.POINTER(C.c_uint), c_int, C.POINTER(c_vp)],
     "stream_get_cu_mask": [c_vp, C.POINTER(C.c_uint), c_int],
     "stream_destroy": [c_vp],
+    "lpips_prep": [c_vp, c_ll, c_ll, c_ll, c_ll, c_vp, c_int, c_int, c_int, c_vp],
+    "relu_f16": [c_vp, c_ll, c_vp],
+    "relu_maxpool2x2_f16": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp],
+    "lpips_distance": [c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int, c_vp, c_ll, c_vp, c_int, c_vp],
 }
 
 INT_FUNCS = {"gemm_select_tile": [c_int] * 3, "gemm_select_split": [c_int] * 5 + [c_ll],
@@ -246,6 +250,7 @@ LL_FUNCS = {
     "mapper_save_floats": [c_int] * 3,
     "mapper_rowgrad_floats": [c_int] * 4,
     "mapper_legacy_input_params": [c_int] * 2,
+    "lpips_ws_floats": [c_int] * 3,
 }
 
 

@@ -429,6 +429,44 @@ def gemm_select_tile(M, N, batch=1):
     return int(fn(M, N, batch))
 
 
+# ------------------------------------------------------------------ LPIPS-VGG glue (csrc/lpips.hip)
+def lpips_prep(x, out, Bn, H, W):
+    """f32 (Bn, 3, H, W) in [-1, 1], any strides -> scaled conv1_1 im2col rows out[Bn*H*W][64] (16-bit)"""
+    assert x.dtype == torch.float32 and x.shape == (Bn, 3, H, W)
+    assert out.is_contiguous() and out.numel() >= Bn * H * W * 64
+    _l.call("lpips_prep", _p(x), *x.stride(), _p(out), Bn, H, W, stream())
+
+
+def relu_(x):
+    """in place on a contiguous 16-bit tensor"""
+    assert x.is_contiguous()
+    _l.call("relu_f16", _p(x), x.numel(), stream())
+
+
+def relu_maxpool2x2(x, out, Bn, H, W, Cc):
+    """NHWC pre-activation [Bn*H*W][Cc] -> relu(max_pool2d(2)) [Bn*(H//2)*(W//2)][Cc] (floor)"""
+    assert x.is_contiguous() and out.is_contiguous() and x.numel() >= Bn * H * W * Cc
+    assert out.numel() >= Bn * (H // 2) * (W // 2) * Cc
+    _l.call("relu_maxpool2x2_f16", _p(x), _p(out), Bn, H, W, Cc, stream())
+
+
+def lpips_ws_floats(P, Cc, HW):
+    n = _l.call_ll("lpips_ws_floats", P, Cc, HW)
+    if n < 0:
+        raise RuntimeError(f"lpips_distance: unsupported shape P={P} C={Cc} HW={HW}")
+    return n
+
+
+def lpips_distance(feat, n_img, pairs, w, Cc, HW, ws, out, accumulate=False):
+    """out[p] (+)= spatial mean of the LPIPS layer distance of feature images pairs[p] (int32 [P, 2], device)"""
+    P = pairs.shape[0]
+    assert pairs.dtype == torch.int32 and pairs.is_contiguous() and pairs.shape == (P, 2)
+    assert feat.is_contiguous() and feat.numel() >= n_img * HW * Cc and w.dtype == torch.float32 and w.numel() == Cc
+    assert out.dtype == torch.float32 and out.numel() >= P and ws.dtype == torch.float32
+    _l.call("lpips_distance", _p(feat), n_img, _p(pairs), P, _p(w), Cc, HW, _p(ws), ws.numel(), _p(out),
+            1 if accumulate else 0, stream())
+
+
 # ------------------------------------------------------------------ device-side input pipeline (csrc/image.hip)
 def img_resample_ksize(in_size, out_size, filt):
     fn = _l.load().vneti_img_resample_ksize
