@@ -5,7 +5,8 @@ against the CPU oracle on bf16-rounded weights.
 
 Bars: bf16 keeps 8 significant bits where fp16 keeps 11, so one rounding is 8x coarser (2^-9 = 2e-3 relative) and the
 north star's 1e-3 (stated for fp16) becomes 8e-3 on the loss; the mapper gradient has to point the same way (cosine
->= 0.995) — a transposed operand, a wrong MFMA opcode or f16 bits read as bf16 give O(1) errors."""
+>= 0.995) — a transposed operand, a wrong MFMA opcode or f16 bits read as bf16 give O(1) errors.  What these bars cannot
+see, a kernel that is subtly wrong in bf16 only, is tests/test_kernels_bf16_gpu.py's job: per-kernel parity of the bf16 library."""
 import json
 import os
 import subprocess
