@@ -422,7 +422,7 @@ __global__ __launch_bounds__(256) void grads_check_finite_segments_kernel(const 
   bool bad = false;
   if (i < seg_len) {
     float x = g[(long long)active[blockIdx.y] * seg_len + i];
-    bad = !(fabsf(x) <= 3.0e38f);
+    bad = !(x == x) || fabsf(x) == INFINITY;  // torch's isfinite, as grads_check_finite_kernel: 3.2e38 is a finite gradient
   }
   if (__any(bad) && (threadIdx.x & 63) == 0) scaler[2] = 1.f;
 }
