@@ -314,7 +314,8 @@ int vneti_add_noise(const float* latents, const float* noise, const void* timest
  * [0,B*HW) unconditional, [B*HW,2B*HW) conditional) and one sampler step in data-prediction form
  *   e = u + g (c - u);  x0 = (x - sigma_t e)/alpha_t  (epsilon)  |  alpha_t x - sigma_t e  (v_prediction)
  *   x <- cx x + c0 x0 + c1 m_prev;  m_prev <- x0;  x_in[2B] <- x (both CFG halves of the next UNet input)
- * which covers DPM-Solver++(2M) (DPMSolverMultistepScheduler, training/validate.py:568) and DDIM (eta = 0);
+ * which covers DPM-Solver++(2M) (DPMSolverMultistepScheduler, training/validate.py:568) and DDIM (eta = 0; eta > 0:
+ * vneti_cfg_sampler_step_noise below);
  * the per-step scalars come from the host (view_neti_amd/engine/infer.py::step_coefficients).
  * x, m_prev: f32 NCHW [B][Lc][HW]; x_in: f32 NCHW [2B][Lc][HW]; pred: f16 NHWC. */
 int vneti_cfg_sampler_step(const void* pred, long long ldp, float* x, float* m_prev, float* x_in, int Bn,
@@ -326,6 +327,23 @@ int vneti_cfg_sampler_step(const void* pred, long long ldp, float* x, float* m_p
 int vneti_cfg_sampler_step_table(const void* pred, long long ldp, float* x, float* m_prev, float* x_in,
                                  int Bn, int Lc, int HW, float guidance, const float* coef_table,
                                  const int* step, int v_prediction, void* stream);
+/* Stochastic DDIM (eta > 0) for the same loop (sd_pipeline_call.py:72-103: `eta` reaches `scheduler.step` through
+ * `prepare_extra_step_kwargs`, :66,101).  DDIMScheduler.step with a_t = alphas_cumprod[t], a_prev of the previous timestep:
+ *   std = eta sqrt((1 - a_prev)/(1 - a_t) (1 - a_t/a_prev));  eps = (x - sqrt(a_t) x0)/sqrt(1 - a_t)
+ *   x_prev = sqrt(a_prev) x0 + sqrt(1 - a_prev - std^2) eps + std noise
+ * which in the data-prediction form of the step above is one more term,
+ *   x <- cx x + c0 x0 + c1 m_prev + cn noise      (cn = std; view_neti_amd/engine/infer.py::ddim_eta_coefficients)
+ * with e, x0, m_prev and x_in exactly as in vneti_cfg_sampler_step; cn = 0 gives that entry's x, m_prev and x_in bit for
+ * bit.  noise: f32 NCHW [B][Lc][HW], the N(0,1) `variance_noise` of this step (drawn by the caller's generator).
+ * 2 B Lc HW 4 bytes (x_in) must stay under the 2 GiB range of the buffer stores. */
+int vneti_cfg_sampler_step_noise(const void* pred, long long ldp, float* x, float* m_prev, float* x_in,
+                                 const float* noise, int Bn, int Lc, int HW, float guidance, float alpha_t,
+                                 float sigma_t, float cx, float c0, float c1, float cn, int v_prediction, void* stream);
+/* hipGraph-replayable form: the scalars {alpha_t, sigma_t, cx, c0, c1, cn} are row step[0] of a device table (T x 6
+ * floats) and the noise is row step[0] of noise_table, f32 [T][B][Lc][HW] (one row under 2 GiB). */
+int vneti_cfg_sampler_step_noise_table(const void* pred, long long ldp, float* x, float* m_prev, float* x_in, int Bn,
+                                       int Lc, int HW, float guidance, const float* coef_table,
+                                       const float* noise_table, const int* step, int v_prediction, void* stream);
 int vneti_table_fill_i64(void* dst_i64, int n, const void* table_i64, const int* step, void* stream);
 int vneti_counter_advance(int* counter, void* stream);
 /* AutoencoderKL.post_quant_conv on the latents scaled by 1/scaling_factor (pipeline.decode_latents):

@@ -13,6 +13,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--model", default="sd21"); ap.add_argument("--resolution", type=int, default=768)
 ap.add_argument("--batch", type=int, default=1); ap.add_argument("--steps", type=int, default=50)
 ap.add_argument("--sampler", default="ddim"); ap.add_argument("--reps", type=int, default=2)
+ap.add_argument("--eta", type=float, default=0.0)  # DDIM only: > 0 runs the noise-table step (stochastic DDIM)
 ap.add_argument("--height", type=int, default=0); ap.add_argument("--width", type=int, default=0)  # default: resolution^2
 a = ap.parse_args()
 a.height, a.width = a.height or a.resolution, a.width or a.resolution
@@ -34,14 +35,16 @@ neg = synth.input_ids(1, ph, cfg.clip.vocab_size); neg[neg == ph] = 7
 eng.set_negative_prompt(neg)
 eng.set_prompt(ids, torch.full((a.batch,), ph), torch.full((a.batch,), phv), synth.gaussian((a.batch, 12), 9).clamp(-1, 1))
 lat = synth.gaussian((a.batch, 4, a.height // 8, a.width // 8), 17)
+# the variance noise of eta > 0 is the caller's draw (sd_pipeline_call: the generator's); its upload is part of a generation
+kw = dict(eta=a.eta, step_noise=torch.randn(a.steps, *lat.shape, generator=torch.Generator().manual_seed(1))) if a.eta else {}
 build_s = time.time() - t0
-img = eng.generate(lat, a.steps, 7.5, a.sampler); torch.cuda.synchronize()
+img = eng.generate(lat, a.steps, 7.5, a.sampler, **kw); torch.cuda.synchronize()
 t0 = time.perf_counter()
 for _ in range(a.reps):
-    img = eng.generate(lat, a.steps, 7.5, a.sampler)
+    img = eng.generate(lat, a.steps, 7.5, a.sampler, **kw)
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / a.reps
 print(json.dumps({"metric": f"NeTI inference images/s ({a.model} {a.width}x{a.height}, {a.sampler}-{a.steps}, CFG, bs={a.batch})",
-                  "value": a.batch / dt, "unit": "images/s", "s_per_image": dt / a.batch, "ms_per_sampler_step": dt / a.steps * 1e3,
+                  "value": a.batch / dt, "unit": "images/s", "eta": a.eta, "s_per_image": dt / a.batch, "ms_per_sampler_step": dt / a.steps * 1e3,
                   "engine_gib": eng.memory_bytes() / 2 ** 30, "build_s": build_s, "image_finite": bool(torch.isfinite(img).all()),
                   "image_mean": float(img.mean())}))

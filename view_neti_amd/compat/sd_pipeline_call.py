@@ -13,6 +13,10 @@
                        randn((1, 4, h, w), generator[i]), the draw a B = 1 call with that generator makes
     height / width  -> fixed at engine construction; passing different values raises
     scheduler       -> `pipeline.sampler` ("dpm++2m" as installed by validate.py:568, or "ddim")
+    eta             -> DDIMScheduler.step's eta (prepare_extra_step_kwargs, sd_pipeline_call.py:66,101); eta > 0 draws one
+                       randn((B, 4, h, w)) per sampler step from `generator`, after the initial latents and in step order
+                       (a list of B generators: (1, 4, h, w) each from its own), as the scheduler's `variance_noise`;
+                       with "dpm++2m" a non-zero eta raises (that scheduler has no eta; the reference drops it silently)
 Returns an object with `.images` (list of PIL images, `output_type="pil"`) or the array, like the reference.
 """
 from __future__ import annotations
@@ -23,7 +27,7 @@ from typing import Any, Dict, List, Optional, Union
 import numpy as np
 import torch
 
-from ..engine.infer import InferenceEngine
+from ..engine.infer import InferenceEngine, check_eta
 from .prompt_manager import PromptEmbeds
 
 
@@ -69,6 +73,16 @@ def set_prompt_list(pipeline: InferencePipeline, prompts: List[PromptEmbeds]) ->
     eng.set_prompts(ids, po, pv, vp, slots, [p.truncation_idx for p in prompts])
 
 
+def _randn(eng: InferenceEngine, generator) -> torch.Tensor:
+    """diffusers' randn_tensor for a latent-shaped draw: one generator draws the whole batch, a list of B draws
+    (1, 4, h, w) each, so that sample i depends on generator[i] alone"""
+    if isinstance(generator, list):
+        if len(generator) != eng.B:
+            raise ValueError(f"{len(generator)} generators for a batch of {eng.B}")
+        return torch.cat([torch.randn((1, eng.Lc, eng.h, eng.w), generator=g, dtype=torch.float32) for g in generator])
+    return torch.randn((eng.B, eng.Lc, eng.h, eng.w), generator=generator, dtype=torch.float32)
+
+
 @torch.no_grad()
 def sd_pipeline_call(pipeline: InferencePipeline, prompt_embeds: Union[PromptEmbeds, List[Dict[str, Any]], Dict[str, Any],
                                                                        torch.Tensor], height: Optional[int] = None,
@@ -84,34 +98,30 @@ def sd_pipeline_call(pipeline: InferencePipeline, prompt_embeds: Union[PromptEmb
         raise ValueError(f"the engine was built for {H}x{W}")
     if num_images_per_prompt != B:
         raise ValueError(f"the engine was built for {B} images per call (num_images_per_prompt={num_images_per_prompt})")
-    if eta != 0.0:
-        raise NotImplementedError("eta > 0 (stochastic DDIM) is not implemented")
+    noisy = check_eta(pipeline.sampler, eta)  # eta != 0 on a sampler without one: ValueError, before any draw
     neg = get_neg_prompt_input_ids(pipeline, negative_prompt)
     eng.set_negative_prompt(neg.input_ids)
     if latents is None:  # pipeline.prepare_latents: randn(shape, generator) * init_noise_sigma (= 1)
-        if isinstance(generator, list):
-            if len(generator) != B:
-                raise ValueError(f"{len(generator)} generators for a batch of {B}")
-            latents = torch.cat([torch.randn((1, eng.Lc, eng.h, eng.w), generator=g, dtype=torch.float32)
-                                 for g in generator])
-        else:
-            latents = torch.randn((B, eng.Lc, eng.h, eng.w), generator=generator, dtype=torch.float32)
+        latents = _randn(eng, generator)
+    # DDIMScheduler.step draws its variance noise inside the loop, after prepare_latents: one draw per step, in step order
+    extra = dict(eta=eta, step_noise=torch.stack([_randn(eng, generator) for _ in range(num_inference_steps)])) \
+        if noisy else {}
     if isinstance(prompt_embeds, list) and prompt_embeds and all(isinstance(p, PromptEmbeds) for p in prompt_embeds):
         # one prompt per sample (distinct from the reference's list of per-step dicts: dispatch on the element type)
         set_prompt_list(pipeline, prompt_embeds)
         out = eng.generate(latents.to(eng.dev), num_inference_steps, guidance_scale, pipeline.sampler,
-                           decode=output_type != "latent")
+                           decode=output_type != "latent", **extra)
     elif isinstance(prompt_embeds, PromptEmbeds):
         rep = lambda t: None if t is None else t.expand(B, *t.shape[1:]) if t.dim() > 1 else t.expand(B)
         eng.set_prompt(rep(prompt_embeds.input_ids), rep(prompt_embeds.input_ids_placeholder_object),
                        rep(prompt_embeds.input_ids_placeholder_view), rep(prompt_embeds.view_params),
                        prompt_embeds.truncation_idx)
         out = eng.generate(latents.to(eng.dev), num_inference_steps, guidance_scale, pipeline.sampler,
-                           decode=output_type != "latent")
+                           decode=output_type != "latent", **extra)
     elif isinstance(prompt_embeds, (list, dict, torch.Tensor)):
         # the reference's contract: conditioning computed by the caller, `prompt_embeds[i]` per step when a list (:86)
         out = eng.generate_from_contexts(latents.to(eng.dev), prompt_embeds, num_inference_steps, guidance_scale,
-                                         pipeline.sampler, decode=output_type != "latent")
+                                         pipeline.sampler, decode=output_type != "latent", **extra)
     else:
         raise TypeError(f"prompt_embeds of type {type(prompt_embeds).__name__}: expected PromptEmbeds, a list of per-step "
                         "context dicts, one dict or one tensor")

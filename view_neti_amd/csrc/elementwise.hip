@@ -294,6 +294,86 @@ __global__ void cfg_sampler_step_table_kernel(const half_t* pred, long long ldp,
   x_in[gid] = xn;
   x_in[(long long)total + gid] = xn;
 }
+// stochastic DDIM (eta > 0): the same step plus the scheduler's variance term,  x <- cx x + c0 x0 + c1 m_prev + cn noise,
+// noise: one f32 NCHW [B][Lc][HW] row of N(0,1) draws (DDIMScheduler.step's `variance_noise`).  Each thread owns V
+// consecutive pixels of one (b, c) plane: V = 4 moves x, m_prev and noise as one 16-byte load each and writes the four
+// output planes with 16-byte write-through stores (the next launches, the UNet's conv_in and the next step, read them);
+// V = 1 serves an HW that is no multiple of 4 or unaligned buffers.  cn == 0 returns r itself, and eta = 0 must reproduce
+// cfg_sampler_step_kernel bit for bit.  The same C++ expressions do not: under the default -ffp-contract=fast the compiler
+// fuses them one way there and another way here (per instantiation: V = 1 fused alpha_t x - sigma_t e into one fma, V = 4
+// split c1 m_prev off into a rounded product and an add).  So contraction is off in this body and every fma of that
+// kernel's ISA is written out: e = fma(g, c-u, u); x0 = fma(-sigma_t, e, x) / alpha_t (IEEE division), or
+// alpha_t x - sigma_t e with both products rounded; r = fma(c1, m_prev, fma(cx, x, c0 x0)).
+struct StepCoef {
+  float alpha_t, sigma_t, cx, c0, c1, cn;
+};
+template <int V>
+__device__ __forceinline__ void cfg_sampler_step_noise_body(const half_t* pred, long long ldp, float* x, float* m_prev,
+                                                            float* x_in, const float* noise, int Bn, int Lc, int HW,
+                                                            float guidance, const StepCoef k, int vpred) {
+#pragma clang fp contract(off)
+  const int total = Bn * Lc * HW;
+  const int gid = (blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (gid >= total) return;
+  const int p = gid % HW;
+  const int c = (gid / HW) % Lc;
+  const int b = gid / (HW * Lc);
+  float xv[V], mp[V], nz[V], x0[V], xn[V];
+  if constexpr (V == 4) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(x + gid);
+    const f32x4 m = *reinterpret_cast<const f32x4*>(m_prev + gid);
+    const f32x4 n = *reinterpret_cast<const f32x4*>(noise + gid);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) xv[j] = a[j], mp[j] = m[j], nz[j] = n[j];
+  } else {
+    xv[0] = x[gid], mp[0] = m_prev[gid], nz[0] = noise[gid];
+  }
+  const half_t* pu = pred + ((long long)b * HW + p) * ldp + c;
+  const half_t* pc = pred + ((long long)(Bn + b) * HW + p) * ldp + c;
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    float u = (float)pu[j * ldp];
+    float cnd = (float)pc[j * ldp];
+    float e = fmaf(guidance, cnd - u, u);
+    x0[j] = vpred ? (k.alpha_t * xv[j] - k.sigma_t * e) : fmaf(-k.sigma_t, e, xv[j]) / k.alpha_t;
+    float r = fmaf(k.c1, mp[j], fmaf(k.cx, xv[j], k.c0 * x0[j]));
+    xn[j] = k.cn != 0.f ? fmaf(k.cn, nz[j], r) : r;
+  }
+  if constexpr (V == 4) {
+    const f32x4 o = {xn[0], xn[1], xn[2], xn[3]}, d = {x0[0], x0[1], x0[2], x0[3]};
+    const uint32_t plane = (uint32_t)total * 4u, off = (uint32_t)gid * 4u;  // launcher: 2 * plane < 2 GiB
+    vn_st16_wt(vn_make_rsrc(x, plane), off, o);
+    vn_st16_wt(vn_make_rsrc(m_prev, plane), off, d);
+    const __amdgpu_buffer_rsrc_t ri = vn_make_rsrc(x_in, 2u * plane);
+    vn_st16_wt(ri, off, o);
+    vn_st16_wt(ri, plane + off, o);
+  } else {
+    x[gid] = xn[0];
+    m_prev[gid] = x0[0];
+    x_in[gid] = xn[0];
+    x_in[(long long)total + gid] = xn[0];
+  }
+}
+template <int V>
+__global__ __launch_bounds__(256) void cfg_sampler_step_noise_kernel(const half_t* pred, long long ldp, float* x,
+                                                                     float* m_prev, float* x_in, const float* noise,
+                                                                     int Bn, int Lc, int HW, float guidance, StepCoef k,
+                                                                     int vpred) {
+  cfg_sampler_step_noise_body<V>(pred, ldp, x, m_prev, x_in, noise, Bn, Lc, HW, guidance, k, vpred);
+}
+// graph-replayable: row step[0] of the T x 6 table {alpha_t, sigma_t, cx, c0, c1, cn} and of the [T][B][Lc][HW] noise table
+template <int V>
+__global__ __launch_bounds__(256) void cfg_sampler_step_noise_table_kernel(const half_t* pred, long long ldp, float* x,
+                                                                           float* m_prev, float* x_in, int Bn, int Lc,
+                                                                           int HW, float guidance, const float* coef_table,
+                                                                           const float* noise_table, const int* step,
+                                                                           int vpred) {
+  const int s = step[0];
+  const float* cf = coef_table + 6 * s;
+  const StepCoef k = {cf[0], cf[1], cf[2], cf[3], cf[4], cf[5]};
+  cfg_sampler_step_noise_body<V>(pred, ldp, x, m_prev, x_in, noise_table + (long long)s * Bn * Lc * HW, Bn, Lc, HW,
+                                 guidance, k, vpred);
+}
 __global__ void table_fill_i64_kernel(long long* dst, int n, const long long* table, const int* step) {
   int gid = blockIdx.x * blockDim.x + threadIdx.x;
   if (gid < n) dst[gid] = table[step[0]];
@@ -598,6 +678,49 @@ extern "C" int vneti_cfg_sampler_step_table(const void* pred, long long ldp, flo
   hipLaunchKernelGGL(cfg_sampler_step_table_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ST, (const half_t*)pred, ldp, x,
                      m_prev, x_in, Bn, Lc, HW, guidance, coef_table, step, v_prediction);
   return vneti_check_launch("cfg_sampler_step_table");
+}
+
+// 16-byte path: whole float4 groups inside one (b, c) plane and 16-byte aligned f32 buffers (any torch allocation is)
+static bool step_noise_vec4(int HW, const void* x, const void* m_prev, const void* x_in, const void* noise) {
+  return HW % 4 == 0 && (((uintptr_t)x | (uintptr_t)m_prev | (uintptr_t)x_in | (uintptr_t)noise) & 15u) == 0;
+}
+
+extern "C" int vneti_cfg_sampler_step_noise(const void* pred, long long ldp, float* x, float* m_prev, float* x_in,
+                                            const float* noise, int Bn, int Lc, int HW, float guidance, float alpha_t,
+                                            float sigma_t, float cx, float c0, float c1, float cn, int v_prediction,
+                                            void* stream) {
+  VN_REQUIRE(pred && x && m_prev && x_in && noise && Bn > 0 && Lc > 0 && HW > 0 && alpha_t > 0.f,
+             "cfg_sampler_step_noise: bad arguments");
+  const long long n = (long long)Bn * Lc * HW;
+  VN_REQUIRE_OUT("cfg_sampler_step_noise (x_in)", 2 * n * 4);
+  const StepCoef k = {alpha_t, sigma_t, cx, c0, c1, cn};
+  if (step_noise_vec4(HW, x, m_prev, x_in, noise))
+    hipLaunchKernelGGL(cfg_sampler_step_noise_kernel<4>, dim3(cdiv((int)(n / 4), 256)), dim3(256), 0, ST,
+                       (const half_t*)pred, ldp, x, m_prev, x_in, noise, Bn, Lc, HW, guidance, k, v_prediction);
+  else
+    hipLaunchKernelGGL(cfg_sampler_step_noise_kernel<1>, dim3(cdiv((int)n, 256)), dim3(256), 0, ST, (const half_t*)pred,
+                       ldp, x, m_prev, x_in, noise, Bn, Lc, HW, guidance, k, v_prediction);
+  return vneti_check_launch("cfg_sampler_step_noise");
+}
+
+extern "C" int vneti_cfg_sampler_step_noise_table(const void* pred, long long ldp, float* x, float* m_prev, float* x_in,
+                                                  int Bn, int Lc, int HW, float guidance, const float* coef_table,
+                                                  const float* noise_table, const int* step, int v_prediction,
+                                                  void* stream) {
+  VN_REQUIRE(pred && x && m_prev && x_in && coef_table && noise_table && step && Bn > 0 && Lc > 0 && HW > 0,
+             "cfg_sampler_step_noise_table: bad arguments");
+  const long long n = (long long)Bn * Lc * HW;
+  VN_REQUIRE_OUT("cfg_sampler_step_noise_table (noise_table row)", n * 4);
+  VN_REQUIRE_OUT("cfg_sampler_step_noise_table (x_in)", 2 * n * 4);
+  if (step_noise_vec4(HW, x, m_prev, x_in, noise_table))
+    hipLaunchKernelGGL(cfg_sampler_step_noise_table_kernel<4>, dim3(cdiv((int)(n / 4), 256)), dim3(256), 0, ST,
+                       (const half_t*)pred, ldp, x, m_prev, x_in, Bn, Lc, HW, guidance, coef_table, noise_table, step,
+                       v_prediction);
+  else
+    hipLaunchKernelGGL(cfg_sampler_step_noise_table_kernel<1>, dim3(cdiv((int)n, 256)), dim3(256), 0, ST,
+                       (const half_t*)pred, ldp, x, m_prev, x_in, Bn, Lc, HW, guidance, coef_table, noise_table, step,
+                       v_prediction);
+  return vneti_check_launch("cfg_sampler_step_noise_table");
 }
 
 extern "C" int vneti_table_fill_i64(void* dst, int n, const void* table, const int* step, void* stream) {

@@ -11,8 +11,9 @@ then  image = (decode(x / scaling)/2 + 0.5).clamp(0,1)                          
 What differs from the reference on purpose: the two UNet calls of a step run as one batch of 2B (the reference
 runs them back to back, :78-94); the T x 16 text-encoder passes are not materialised up front (the reference
 holds T dicts of 32 tensors) but produced per step, 16 layers at a time; the unconditional embedding is computed
-once.  Samplers: DPM-Solver++(2M) (the scheduler validate.py:568 / inference_dtu.py:304 install) and DDIM
-(eta 0), both as x <- cx x + c0 x0 + c1 x0_prev on the data prediction.
+once.  Samplers: DPM-Solver++(2M) (the scheduler validate.py:568 / inference_dtu.py:304 install) and DDIM,
+both as x <- cx x + c0 x0 + c1 x0_prev on the data prediction; DDIM with eta > 0 adds cn * noise, the noise of each step
+read from a device table so that the step still replays as one graph (vneti_cfg_sampler_step_noise_table).
 """
 from __future__ import annotations
 
@@ -63,6 +64,38 @@ def step_coefficients(kind: str, ac: torch.Tensor, timesteps: Sequence[int], i: 
         return float(cx), float(base), 0.0, float(al[t]), float(sg[t])
     r0 = (lam[t] - lam[timesteps[i - 1]]) / h
     return float(cx), float(base * (1 + 0.5 / r0)), float(-0.5 * base / r0), float(al[t]), float(sg[t])
+
+
+def ddim_eta_coefficients(ac: torch.Tensor, timesteps: Sequence[int], i: int, eta: float):
+    """(alpha_t, sigma_t, cx, c0, c1, cn) of DDIM step i with the scheduler's `eta` (one row of the 6-column device table),
+    f64 on the host.  DDIMScheduler.step, set_alpha_to_one=False:
+        std = eta sqrt((1 - a_prev)/(1 - a_t) (1 - a_t/a_prev))
+        x_prev = sqrt(a_prev) x0 + sqrt(1 - a_prev - std^2) eps + std noise,   eps = (x - sqrt(a_t) x0)/sqrt(1 - a_t)
+    i.e. x <- cx x + c0 x0 + cn noise with r = sqrt((1 - a_prev - std^2)/(1 - a_t)): cx = r, c0 = sqrt(a_prev) - r sqrt(a_t),
+    cn = std.  eta = 0 gives step_coefficients("ddim", ...) exactly (std^2 = 0 leaves every operation as it is there)."""
+    if eta < 0:
+        raise ValueError(f"eta = {eta}: DDIM's eta lies in [0, 1] (0: deterministic, 1: DDPM-like variance)")
+    ac = ac.double().cpu()
+    t = timesteps[i]
+    tp = t - ac.numel() // len(timesteps)
+    a_t = ac[t]
+    a_p = ac[tp] if tp >= 0 else ac[0]
+    std = float(eta) * ((1 - a_p) / (1 - a_t) * (1 - a_t / a_p)).sqrt()
+    r = ((1 - a_p - std ** 2) / (1 - a_t)).sqrt()
+    return (float(a_t.sqrt()), float((1 - a_t).sqrt()), float(r), float(a_p.sqrt() - r * a_t.sqrt()), 0.0, float(std))
+
+
+def check_eta(kind: str, eta: float) -> bool:
+    """True when the step needs the noise term.  DPMSolverMultistepScheduler.step takes no `eta`: the reference's
+    prepare_extra_step_kwargs drops it silently there; here asking for it is an error rather than a deterministic run."""
+    if eta == 0.0:
+        return False
+    if kind != "ddim":
+        raise ValueError(f"eta = {eta} with the {kind!r} sampler: only DDIM has an eta (the reference's "
+                         "DPMSolverMultistepScheduler ignores the argument); use sampler 'ddim' or eta = 0")
+    if eta < 0:
+        raise ValueError(f"eta = {eta}: DDIM's eta lies in [0, 1]")
+    return True
 
 
 _BUFFER_RANGE = 0x7fffffff  # bytes a buffer-resource store can address (csrc/common.h VN_REQUIRE_OUT)
@@ -162,6 +195,12 @@ class InferenceEngine:
         self.ts_table = torch.zeros((cfg.ddpm.num_train_timesteps,), dtype=torch.int64, device=device)
         self._graph = None
         self._graph_key = None
+        # stochastic DDIM (eta > 0): a 6-column table (+ cn) and the per-step variance noise [T][B][Lc][h][w], allocated
+        # at the first such call; the captured step that reads them is cached beside the eta = 0 one
+        self.coef_table6 = torch.zeros((cfg.ddpm.num_train_timesteps, 6), dtype=torch.float32, device=device)
+        self.noise_table = None
+        self._graph_noise = None
+        self._graph_noise_key = None
 
     # ------------------------------------------------------------------ conditioning
     def set_negative_prompt(self, input_ids: torch.Tensor):
@@ -217,13 +256,18 @@ class InferenceEngine:
     # ------------------------------------------------------------------ the loop
     @torch.no_grad()
     def generate(self, latents: torch.Tensor, num_inference_steps: int = 50, guidance_scale: float = 7.5,
-                 kind: str = "dpm++2m", decode: bool = True, use_graph: bool = True):
+                 kind: str = "dpm++2m", decode: bool = True, use_graph: bool = True, eta: float = 0.0,
+                 step_noise: Optional[torch.Tensor] = None):
         """latents: (B, 4, h, w) N(0,1) draw (`prepare_latents`, init_noise_sigma = 1 for both samplers).
+        eta > 0 (DDIM only): DDIMScheduler.step's variance term, fed from step_noise, f32 [T][B][4][h][w] N(0,1) (one draw
+        per sampler step; None: drawn here from torch's global generator, as the scheduler does without a generator).
         Returns the images f32 [B, H, W, 3] in [0,1] (the array `numpy_to_pil` receives) or the final latents."""
         if guidance_scale <= 1.0:
             raise ValueError("sd_pipeline_call only defines the classifier-free-guidance branch (guidance_scale > 1)")
         B, L = self.B, self.L
         ts = inference_timesteps(kind, num_inference_steps, self.cfg.ddpm.num_train_timesteps)
+        if check_eta(kind, eta):
+            return self._generate_eta(latents, ts, guidance_scale, decode, use_graph, eta, step_noise)
         self.x.copy_(latents)
         self.m_prev.zero_()
         self.unet.x_in[:B].copy_(self.x)
@@ -307,7 +351,8 @@ class InferenceEngine:
 
     @torch.no_grad()
     def generate_from_contexts(self, latents: torch.Tensor, prompt_embeds, num_inference_steps: int = 50,
-                               guidance_scale: float = 7.5, kind: str = "dpm++2m", decode: bool = True):
+                               guidance_scale: float = 7.5, kind: str = "dpm++2m", decode: bool = True,
+                               eta: float = 0.0, step_noise: Optional[torch.Tensor] = None):
         """`sd_pipeline_call` with the conditioning ALREADY computed, exactly as the reference passes it
         (sd_pipeline_call.py:86: `prompt_embeds[i] if type(prompt_embeds) == list else prompt_embeds`): a list of T
         per-step XTI dicts (PromptManager.embed_prompt's return value, prompt_manager.py:79-99), one dict, or one tensor.
@@ -323,6 +368,9 @@ class InferenceEngine:
         self.unet.x_in[:B].copy_(self.x)
         self.unet.x_in[B:].copy_(self.x)
         vpred = self.cfg.ddpm.prediction_type == "v_prediction"
+        noisy = check_eta(kind, eta)
+        if noisy:
+            self._load_step_noise(step_noise, len(ts))
         if type(prompt_embeds) != list:
             self.load_contexts(prompt_embeds)
         for i, t in enumerate(ts):
@@ -330,6 +378,9 @@ class InferenceEngine:
                 self.load_contexts(prompt_embeds[i])
             self.unet.timesteps.fill_(t)
             self.unet.forward()
+            if noisy:
+                self._eager_noise_step(ts, i, guidance_scale, vpred, eta)
+                continue
             cx, c0, c1, a_t, s_t = step_coefficients(kind, self.ac, ts, i)
             ops.cfg_sampler_step(self.unet.pred, self.x, self.m_prev, self.unet.x_in, B, self.Lc, self.h * self.w,
                                  guidance_scale, a_t, s_t, cx, c0, c1, vpred)
@@ -337,7 +388,65 @@ class InferenceEngine:
             return self.x
         return self.decode()
 
-    def _one_step(self, guidance_scale, vpred):
+    # ------------------------------------------------------------------ stochastic DDIM (eta > 0)
+    def _load_step_noise(self, step_noise: Optional[torch.Tensor], T: int) -> None:
+        """upload the variance noise of T steps into the device table (grown, never shrunk: a captured step holds its
+        address, so a new allocation drops that graph)"""
+        shape = (T, self.B, self.Lc, self.h, self.w)
+        if step_noise is None:
+            step_noise = torch.randn(shape, dtype=torch.float32)
+        if tuple(step_noise.shape) != shape or step_noise.dtype != torch.float32:
+            raise ValueError(f"step_noise of shape {tuple(step_noise.shape)} {step_noise.dtype}: expected f32 {shape}")
+        if self.noise_table is None or self.noise_table.shape[0] < T:
+            self.noise_table = torch.empty(shape, dtype=torch.float32, device=self.dev)
+            self._graph_noise = None
+        self.noise_table[:T].copy_(step_noise)
+
+    def _eager_noise_step(self, ts, i, guidance_scale, vpred, eta):
+        a_t, s_t, cx, c0, c1, cn = ddim_eta_coefficients(self.ac, ts, i, eta)
+        ops.cfg_sampler_step_noise(self.unet.pred, self.x, self.m_prev, self.unet.x_in, self.noise_table[i], self.B,
+                                   self.Lc, self.h * self.w, guidance_scale, a_t, s_t, cx, c0, c1, cn, vpred)
+
+    def _seed(self, latents):
+        B = self.B
+        self.x.copy_(latents)
+        self.m_prev.zero_()
+        self.unet.x_in[:B].copy_(self.x)
+        self.unet.x_in[B:].copy_(self.x)
+
+    def _generate_eta(self, latents, ts, guidance_scale, decode, use_graph, eta, step_noise):
+        """generate() for DDIM with eta > 0: the same loop with vneti_cfg_sampler_step_noise(_table) as its last launch"""
+        B, L = self.B, self.L
+        self._load_step_noise(step_noise, len(ts))
+        self._seed(latents)
+        vpred = self.cfg.ddpm.prediction_type == "v_prediction"
+        if use_graph:
+            rows = [ddim_eta_coefficients(self.ac, ts, i, eta) for i in range(len(ts))]
+            self.coef_table6[: len(ts)].copy_(torch.tensor(rows, dtype=torch.float32))
+            self.ts_table[: len(ts)].copy_(torch.tensor(ts, dtype=torch.int64))
+            self.step_idx.zero_()
+            key = (guidance_scale, vpred, True)  # eta itself lives in the table: one graph serves every eta > 0
+            if self._graph_noise is None or self._graph_noise_key != key:
+                self._graph_noise = self._capture(guidance_scale, vpred, noise=True)
+                self._graph_noise_key = key
+                self.step_idx.zero_()
+                self._seed(latents)
+            for _ in ts:
+                self._graph_noise.replay()
+        else:
+            for i, t in enumerate(ts):
+                self.t_text.fill_(t)
+                self.unet.timesteps.fill_(t)
+                self.text.forward()
+                self.unet.ctx_k[:, B * L:].copy_(self.ctx_k)
+                self.unet.ctx_v[:, B * L:].copy_(self.ctx_v)
+                self.unet.forward()
+                self._eager_noise_step(ts, i, guidance_scale, vpred, eta)
+        if not decode:
+            return self.x
+        return self.decode()
+
+    def _one_step(self, guidance_scale, vpred, noise=False):
         B, L = self.B, self.L
         ops.table_fill_i64(self.t_text, self.ts_table, self.step_idx)
         ops.table_fill_i64(self.unet.timesteps, self.ts_table, self.step_idx)
@@ -345,22 +454,32 @@ class InferenceEngine:
         self.unet.ctx_k[:, B * L:].copy_(self.ctx_k)
         self.unet.ctx_v[:, B * L:].copy_(self.ctx_v)
         self.unet.forward()
-        ops.cfg_sampler_step_table(self.unet.pred, self.x, self.m_prev, self.unet.x_in, B, self.Lc, self.h * self.w,
-                                   guidance_scale, self.coef_table, self.step_idx, vpred)
+        if noise:
+            ops.cfg_sampler_step_noise_table(self.unet.pred, self.x, self.m_prev, self.unet.x_in, B, self.Lc,
+                                             self.h * self.w, guidance_scale, self.coef_table6, self.noise_table,
+                                             self.step_idx, vpred)
+        else:
+            ops.cfg_sampler_step_table(self.unet.pred, self.x, self.m_prev, self.unet.x_in, B, self.Lc, self.h * self.w,
+                                       guidance_scale, self.coef_table, self.step_idx, vpred)
         ops.counter_advance(self.step_idx)
 
-    def _capture(self, guidance_scale, vpred):
-        """capture one sampler step (the warm-up run below is a real step: the caller re-seeds x afterwards)."""
+    def _capture(self, guidance_scale, vpred, noise=False):
+        """capture one sampler step (the warm-up run below is a real step: the caller re-seeds x afterwards).  The eta = 0
+        step becomes self._graph; the noise-table step is returned to its caller."""
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            self._one_step(guidance_scale, vpred)
+            self._one_step(guidance_scale, vpred, noise)
             torch.cuda.synchronize()
-            self._graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph, stream=s):
-                self._one_step(guidance_scale, vpred)
+            graph = torch.cuda.CUDAGraph()
+            if not noise:
+                self._graph = graph
+            with torch.cuda.graph(graph, stream=s):
+                self._one_step(guidance_scale, vpred, noise)
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
+        return graph
 
     def memory_bytes(self) -> int:
-        return self.unet.bytes + self.text.bytes + self.decoder.bytes
+        noise = 0 if self.noise_table is None else self.noise_table.numel() * 4
+        return self.unet.bytes + self.text.bytes + self.decoder.bytes + noise

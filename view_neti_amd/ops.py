@@ -293,6 +293,20 @@ def cfg_sampler_step_table(pred, x, m_prev, x_in, Bn, Lc, HW, guidance, coef_tab
             _p(coef_table), _p(step), 1 if v_prediction else 0, stream())
 
 
+def cfg_sampler_step_noise(pred, x, m_prev, x_in, noise, Bn, Lc, HW, guidance, alpha_t, sigma_t, cx, c0, c1, cn,
+                           v_prediction):
+    """the step of cfg_sampler_step plus cn * noise (stochastic DDIM); noise: f32 [B][Lc][HW]"""
+    _l.call("cfg_sampler_step_noise", _p(pred), _ld(pred), _p(x), _p(m_prev), _p(x_in), _p(noise), Bn, Lc, HW, guidance,
+            alpha_t, sigma_t, cx, c0, c1, cn, 1 if v_prediction else 0, stream())
+
+
+def cfg_sampler_step_noise_table(pred, x, m_prev, x_in, Bn, Lc, HW, guidance, coef_table, noise_table, step,
+                                 v_prediction):
+    """coef_table: f32 [T][6] {alpha_t, sigma_t, cx, c0, c1, cn}; noise_table: f32 [T][B][Lc][HW]; row step[0] of both"""
+    _l.call("cfg_sampler_step_noise_table", _p(pred), _ld(pred), _p(x), _p(m_prev), _p(x_in), Bn, Lc, HW, guidance,
+            _p(coef_table), _p(noise_table), _p(step), 1 if v_prediction else 0, stream())
+
+
 def table_fill_i64(dst, table, step):
     _l.call("table_fill_i64", _p(dst), dst.numel(), _p(table), _p(step), stream())
 
