@@ -157,7 +157,7 @@ int vneti_transpose_f16(const void* in, long long ld_in, long long stride_in, vo
  * an attention backward): fields as the arguments of vneti_transpose_f16. */
 #define VNETI_TRANSPOSE_MAX 4
 typedef struct vneti_transpose_desc {
-  const void* in;
+  const void* inp;
   long long ld_in, stride_in;
   void* out;
   long long ld_out, stride_out;

@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void transpose_multi_kernel(TMulti m) {
   const long long ld_in = d.ld_in, ld_out = d.ld_out;
   const int r0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
   if (r0 >= ld_out || c0 >= cols) return;  // grid is sized for the largest descriptor
-  const half_t* ib = (const half_t*)d.in + (long long)z * d.stride_in;
+  const half_t* ib = (const half_t*)d.inp + (long long)z * d.stride_in;
   half_t* ob = (half_t*)d.out + (long long)z * d.stride_out;
   for (int idx = threadIdx.x; idx < 512; idx += 256) {
     int r = idx >> 3, ch = idx & 7;
@@ -134,7 +134,7 @@ extern "C" int vneti_transpose_f16_multi(const vneti_transpose_desc* descs, int 
   int gx = 0, gy = 0, gz = 0;
   for (int i = 0; i < n; ++i) {
     const vneti_transpose_desc& d = descs[i];
-    VN_REQUIRE(d.in && d.out && d.rows > 0 && d.cols > 0 && d.batch > 0, "transpose_multi[%d]: bad arguments", i);
+    VN_REQUIRE(d.inp && d.out && d.rows > 0 && d.cols > 0 && d.batch > 0, "transpose_multi[%d]: bad arguments", i);
     VN_REQUIRE(d.cols % 8 == 0 && d.ld_in % 8 == 0 && d.ld_out % 8 == 0 && d.ld_out >= d.rows,
                "transpose_multi[%d]: cols/ld must be multiples of 8 and ld_out >= rows", i);
     m.d[i] = d;

@@ -1,4 +1,5 @@
-"""ctypes binding of libvneti_hip.so (the C ABI declared in include/vneti.h).
+"""ctypes binding of libvneti_hip.so, derived from the C ABI declared in include/vneti.h: the header is parsed once at
+import into the argument structs and the signature of every entry point; nothing here restates it by hand.
 
 The product path has NO fallback: if the shared library is missing or a call fails, a
 RuntimeError is raised.  `load()` never builds implicitly on a machine without hipcc; use
@@ -7,6 +8,7 @@ RuntimeError is raised.  `load()` never builds implicitly on a machine without h
 from __future__ import annotations
 
 import ctypes as C
+import keyword
 import os
 import re
 
@@ -53,44 +55,82 @@ def act_dtype():
     import torch
     return torch.bfloat16 if _precision == "bf16" else torch.float16
 
-c_ll = C.c_longlong
-c_vp = C.c_void_p
-c_int = C.c_int
-c_f = C.c_float
+
+_SCALARS = {"int": C.c_int, "long long": C.c_longlong, "float": C.c_float, "unsigned": C.c_uint, "unsigned int": C.c_uint,
+            "uint32_t": C.c_uint, "size_t": C.c_size_t}
 
 
-class TransposeDesc(C.Structure):
-    """Mirror of `vneti_transpose_desc` (include/vneti.h)."""
+def _ctype(ctype: str, structs: dict, where: str):
+    """THE type rule of the binding: a scalar by _SCALARS, `char*` -> c_char_p, a pointer to a struct of the header ->
+    POINTER(its Structure), every other pointer (void*, const float*, unsigned*, void**, ...) -> c_void_p, which takes
+    data_ptr() ints, None, ctypes arrays and byref(...).  Anything else raises: there is no default."""
+    words = [w for w in ctype.replace("*", " * ").split() if w != "const"]
+    stars, base = words.count("*"), " ".join(w for w in words if w != "*")
+    if stars == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    if stars == 1 and base == "char":
+        return C.c_char_p
+    if stars == 1 and base in structs:
+        return C.POINTER(structs[base])
+    if stars and (base in _SCALARS or base in ("void", "char")):
+        return C.c_void_p
+    raise ValueError(f"vneti.h {where}: no ctypes rule for the type {ctype.strip()!r}")
 
-    _fields_ = [("inp", c_vp), ("ld_in", c_ll), ("stride_in", c_ll), ("out", c_vp), ("ld_out", c_ll),
-                ("stride_out", c_ll), ("rows", c_int), ("cols", c_int), ("batch", c_int), ("_pad", c_int)]
+
+def _declarator(decl: str, where: str):
+    """'const void* A' -> ('const void*', 'A')"""
+    m = re.fullmatch(r"(.*[\s*])(\w+)", decl.strip(), re.S)
+    if not m:
+        raise ValueError(f"vneti.h {where}: cannot read the declaration {' '.join(decl.split())!r}")
+    return m.group(1), m.group(2)
 
 
-class GemmDesc(C.Structure):
-    """Mirror of `vneti_gemm_desc` (include/vneti.h)."""
+def parse_header(text: str):
+    """The C ABI in header text -> (structs: C name -> generated ctypes.Structure, prototypes: C name -> (restype, argtypes)).
+    Reads `typedef struct ... { ... } name;` and `int|long long vneti_*(...);`; any other statement raises with its line."""
+    blank = lambda m: "\n" * m.group().count("\n")  # what is cut out keeps its line breaks, so positions still name lines
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", blank, text, flags=re.S)
+    text = re.sub(r'^[ \t]*#.*$|extern\s+"C"\s*\{|^\}[ \t]*$', "", text, flags=re.M)
+    at = lambda src, pos: f"line {src.count(chr(10), 0, pos) + 1}"
+    structs, protos = {}, {}
+    typedef = r"typedef\s+struct\s+\w*\s*\{(.*?)\}\s*(\w+)\s*;"
+    for m in re.finditer(typedef, text, flags=re.S):
+        fields = []
+        for d in re.finditer(r"[^;\s][^;]*", m.group(1)):  # `int Hi, Wi, Ci;` declares one field per name
+            where = at(text, m.start(1) + d.start())
+            first, *more = d.group().split(",")
+            ctype, name = _declarator(first, where)
+            for n in [name] + [x.strip() for x in more]:
+                if not n.isidentifier() or keyword.iskeyword(n):  # `*b`, `a[4]`, or a name python cannot spell as d.<name>
+                    raise ValueError(f"vneti.h {where}: cannot bind the field {n!r}")
+                fields.append((n, _ctype(ctype, structs, where)))
+        structs[m.group(2)] = type(m.group(2), (C.Structure,), {"_fields_": fields})
+    rest = re.sub(typedef, blank, text, flags=re.S)
+    for m in re.finditer(r"[^;\s][^;]*", rest):
+        p = re.fullmatch(r"(int|long long)\s+(vneti_\w+)\s*\((.*)\)\s*", m.group(), re.S)
+        if not p:
+            raise ValueError(f"vneti.h {at(rest, m.start())}: cannot read {' '.join(m.group().split())!r} as a prototype")
+        argtypes = []
+        for x in re.finditer(r"[^,\s][^,]*", "" if p.group(3).strip() == "void" else p.group(3)):
+            where = at(rest, m.start() + p.start(3) + x.start())
+            argtypes.append(_ctype(_declarator(x.group(), where)[0], structs, where))
+        protos[p.group(2)] = (_SCALARS[p.group(1)], argtypes)
+    return structs, protos
 
-    _fields_ = [
-        ("A", c_vp), ("B", c_vp), ("C", c_vp),
-        ("lda", c_ll), ("ldb", c_ll), ("ldc", c_ll),
-        ("M", c_int), ("N", c_int), ("K", c_int),
-        ("batch", c_int),
-        ("strideA", c_ll), ("strideB", c_ll), ("strideC", c_ll),
-        ("bias", c_vp),
-        ("rowadd", c_vp), ("ld_rowadd", c_ll), ("rows_per_group", c_int),
-        ("resid", c_vp), ("ldr", c_ll),
-        ("alpha", c_f), ("act", c_int), ("out_f32", c_int),
-        ("conv_mode", c_int),
-        ("Hi", c_int), ("Wi", c_int), ("Ci", c_int), ("Ho", c_int), ("Wo", c_int),
-        ("stride", c_int), ("pad_t", c_int), ("pad_l", c_int), ("ups", c_int),
-        ("ldx", c_ll),
-        ("tile_hint", c_int),
-        ("workspace", c_vp), ("workspace_bytes", c_ll), ("split_k", c_int),
-        ("gate_src", c_vp), ("ld_gate", c_ll), ("gate_act", c_int),
-        ("C2", c_vp), ("ldc2", c_ll), ("act2", c_int),
-        ("gn_sums", c_vp), ("gn_hw", c_int), ("gn_cpg", c_int), ("gn_groups", c_int), ("gn_slots", c_int),
-        ("geglu", c_int),
-        ("conv_korder", c_int),
-    ]
+
+with open(HEADER_PATH) as _f:
+    _STRUCTS, _PROTOS = parse_header(_f.read())
+GemmDesc, TransposeDesc = _STRUCTS["vneti_gemm_desc"], _STRUCTS["vneti_transpose_desc"]
+# short name -> argtypes of every declared function
+SIGNATURES = {n[len("vneti_"):]: argtypes for n, (_, argtypes) in _PROTOS.items()}
+# the functions whose return value is a number to use (`query`); every other one returns a status (`call`)
+VALUE_FUNCS = frozenset({
+    "version", "precision", "last_error", "gemm_select_tile", "gemm_select_split", "img_resample_ksize",
+    "groupnorm_ws_floats", "lpips_ws_floats", "mapper_num_params", "mapper_save_floats", "mapper_rowgrad_floats",
+    "mapper_legacy_input_params"})
+_stray = ({n[len("vneti_"):] for n, (res, _) in _PROTOS.items() if res is C.c_longlong} - VALUE_FUNCS) | (VALUE_FUNCS - set(SIGNATURES))
+if _stray:
+    raise RuntimeError(f"lib.VALUE_FUNCS is out of step with include/vneti.h: {sorted(_stray)}")
 
 
 def declared_symbols() -> list[str]:
@@ -101,7 +141,8 @@ def declared_symbols() -> list[str]:
 
 
 def load():
-    """Load the library once; raise loudly when it is absent."""
+    """Load the library once and bind every declared function (argtypes and restype from the header); raise loudly when
+    the library or one of its symbols is absent."""
     global _lib
     if _lib is not None:
         return _lib
@@ -110,15 +151,13 @@ def load():
             f"{os.path.basename(SO_PATH)} not found at {SO_PATH}: build it with "
             "`python view_neti_amd/csrc/build.py` (hipcc, gfx950). There is no fallback path.")
     lib = C.CDLL(SO_PATH)
-    lib.vneti_version.restype = c_int
-    lib.vneti_precision.restype = c_int
+    for name, (restype, argtypes) in _PROTOS.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise RuntimeError(f"{SO_PATH} does not export {name}, which include/vneti.h declares: rebuild it")
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.vneti_precision() != _PRECISIONS[_precision][1]:
         raise RuntimeError(f"{SO_PATH} computes in precision {lib.vneti_precision()}, the process asked for {_precision}")
-    lib.vneti_last_error.argtypes = [C.c_char_p, C.c_size_t]
-    lib.vneti_last_error.restype = c_int
-    lib.vneti_groupnorm_ws_floats.restype = c_ll
-    lib.vneti_groupnorm_ws_floats.argtypes = [c_int] * 4
-    lib.vneti_gemm_f16.argtypes = [C.POINTER(GemmDesc), c_vp]
     _lib = lib
     return lib
 
@@ -136,130 +175,13 @@ def check(rc: int, what: str = ""):
 
 
 def call(name: str, *args):
-    """Call `vneti_<name>` with positional args; pointers are ints/None, scalars by python type.
-
-    Argument conversion is explicit per call-site through the typed helpers below; this generic
-    entry is used for the many small elementwise entry points whose signatures are registered
-    in SIGNATURES.
-    """
-    lib = load()
-    fn = getattr(lib, "vneti_" + name)
-    sig = SIGNATURES.get(name)
-    if sig is not None and fn.argtypes is None:
-        fn.argtypes = sig
-        fn.restype = c_int
-    rc = fn(*args)
-    check(rc, name)
+    """Call the status-returning `vneti_<name>`: pointers are data_ptr() ints / None / ctypes arrays / byref(...), scalars
+    python numbers; a non-zero status raises with the library's message."""
+    check(getattr(load(), "vneti_" + name)(*args), name)
 
 
-# argtypes for every int-returning entry point (kept in the same order as include/vneti.h)
-SIGNATURES = {
-    "im2col3x3_small": [c_vp, c_int, c_ll, c_ll, c_ll, c_ll, c_vp] + [c_int] * 9 + [c_vp],
-    "conv3x3_in": [c_vp, c_int, c_ll, c_ll, c_ll, c_ll, c_vp, c_vp, c_vp, c_ll] + [c_int] * 5 + [c_vp, c_int, c_int, c_vp],
-    "transpose_f16": [c_vp, c_ll, c_ll, c_vp, c_ll, c_ll, c_int, c_int, c_int, c_vp],
-    "transpose_f16_multi": [c_vp, c_int, c_vp],
-    "img_resample_coeffs": [c_int, c_int, c_int, c_vp, c_vp, c_vp],
-    "img_resample_pass": [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp],
-    "img_crop": [c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp],
-    "img_enhance": [c_vp, c_int, c_int, c_int, c_f, c_vp, c_vp],
-    "img_hue": [c_vp, c_int, c_int, c_int, c_vp],
-    "img_blur5": [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp],
-    "img_affine_nearest": [c_vp, c_vp, c_int, c_int, c_vp, c_int, c_vp],
-    "img_to_f32_chw": [c_vp, c_vp, c_int, c_int, c_vp],
-    "groupnorm_fwd_sums": [c_vp, c_ll, c_vp, c_ll, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int,
-                           c_f, c_int, c_vp],
-    "groupnorm_fwd": [c_vp, c_ll, c_vp, c_ll, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int,
-                      c_f, c_int, c_vp],
-    "groupnorm_fwd_2l": [c_vp, c_ll, c_vp, c_ll, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int,
-                         c_f, c_int, c_vp],
-    "groupnorm_bwd_2l": [c_vp, c_ll, c_vp, c_ll, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_vp, c_ll, c_vp, c_int, c_vp,
-                         c_int, c_int, c_int, c_int, c_int, c_vp],
-    "groupnorm_bwd": [c_vp, c_ll, c_vp, c_ll, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_vp, c_ll, c_vp,
-                      c_int, c_int, c_int, c_int, c_int, c_vp],
-    "layernorm_fwd": [c_vp, c_int, c_ll, c_vp, c_ll, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_f, c_vp],
-    "layernorm_bwd": [c_vp, c_int, c_ll, c_vp, c_int, c_ll, c_vp, c_vp, c_vp, c_vp, c_int, c_ll, c_vp,
-                      c_ll, c_vp, c_ll, c_int, c_int, c_vp],
-    "attn_fwd": [c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_vp, c_int, c_int, c_int, c_int, c_int,
-                 c_f, c_int, c_vp],
-    "attn_bwd_delta": [c_vp, c_ll, c_vp, c_ll, c_vp, c_int, c_int, c_int, c_int, c_vp],
-    "attn_bwd_dq": [c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_vp, c_vp, c_vp, c_ll, c_vp, c_ll,
-                    c_int, c_int, c_int, c_int, c_int, c_f, c_int, c_vp],
-    "attn_bwd_dkv": [c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_vp, c_vp,
-                     c_vp, c_ll, c_vp, c_ll, c_int, c_int, c_int, c_int, c_int, c_f, c_int, c_vp, c_ll, c_vp],
-    "attn_bwd_small": [c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_vp, c_vp, c_ll, c_vp, c_ll, c_vp, c_ll,
-                       c_int, c_int, c_int, c_int, c_f, c_int, c_vp],
-    "softmax_rows_f16": [c_vp, c_ll, c_int, c_int, c_vp],
-    "add_f16": [c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_int, c_int, c_vp],
-    "geglu_fwd": [c_vp, c_ll, c_vp, c_ll, c_int, c_int, c_vp],
-    "geglu_bwd": [c_vp, c_ll, c_vp, c_ll, c_vp, c_ll, c_int, c_int, c_vp],
-    "act_fwd_f16": [c_vp, c_vp, c_ll, c_int, c_vp],
-    "act_bwd_f16": [c_vp, c_vp, c_vp, c_ll, c_int, c_vp],
-    "timestep_embedding": [c_vp, c_vp, c_int, c_int, c_vp],
-    "sum2x2_f16": [c_vp, c_ll, c_vp, c_ll, c_int, c_int, c_int, c_int, c_vp],
-    "rng_fill_normal": [c_vp, c_ll, c_vp, C.c_uint, c_vp],
-    "rng_fill_randint": [c_vp, c_int, c_int, c_vp, C.c_uint, c_vp],
-    "rng_advance": [c_vp, c_vp],
-    "sample_add_noise": [c_vp, c_ll, c_vp, c_vp, c_vp, c_vp, c_f, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int,
-                         c_vp],
-    "latent_sample": [c_vp, c_ll, c_vp, c_f, c_vp, c_int, c_int, c_int, c_vp],
-    "add_noise": [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp],
-    "cfg_sampler_step": [c_vp, c_ll, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_int, c_vp],
-    "cfg_sampler_step_table": [c_vp, c_ll, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_f, c_vp, c_vp, c_int, c_vp],
-    "cfg_sampler_step_noise": [c_vp, c_ll, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_f,
-                               c_int, c_vp],
-    "cfg_sampler_step_noise_table": [c_vp, c_ll, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_f, c_vp, c_vp, c_vp, c_int, c_vp],
-    "table_fill_i64": [c_vp, c_int, c_vp, c_vp, c_vp],
-    "counter_advance": [c_vp, c_vp],
-    "conv1x1_nchw_f32": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_f, c_vp],
-    "image_postprocess": [c_vp, c_ll, c_vp, c_ll, c_int, c_vp],
-    "mse_loss_grad": [c_vp, c_ll, c_vp, c_vp, c_ll, c_vp, c_vp, c_int, c_int, c_int, c_vp],
-    "adamw_flat": [c_vp, c_vp, c_vp, c_vp, c_ll, c_vp, c_vp, c_vp, c_int, c_int, c_vp],
-    "adamw_segments": [c_vp, c_vp, c_vp, c_vp, c_ll, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp],
-    "nested_dropout_mask": [c_vp, c_int, c_int, c_int, c_f, c_vp, C.c_uint, c_vp],
-    "mapper_fwd": [c_vp, c_vp, c_ll, c_vp, c_int, c_vp, c_vp, c_f, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int,
-                   c_int, c_vp, c_vp],
-    "mapper_bwd": [c_vp, c_vp, c_ll, c_vp, c_f, c_vp, c_vp, c_vp, c_ll, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
-                   c_int, c_int, c_int, c_int, c_vp, c_vp],
-    "mapper_legacy_input_fwd": [c_vp, c_vp, c_ll, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp],
-    "mapper_fwd_slots": [c_vp, c_vp, c_ll, c_int, c_vp, c_int, c_vp, c_vp, c_f, c_vp, c_vp, c_vp, c_int, c_int, c_int,
-                         c_int, c_int, c_vp, c_vp],
-    "mapper_legacy_input_fwd_slots": [c_vp, c_vp, c_ll, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp],
-    "mapper_legacy_input_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_int, c_int, c_int, c_int, c_int, c_vp],
-    "text_embed": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp],
-    "text_final_fwd": [c_vp, c_vp, c_vp, c_f, c_vp, c_vp, c_f, c_int, c_vp, c_vp, c_f, c_int, c_vp, c_vp, c_vp,
-                       c_int, c_int, c_int, c_int, c_vp],
-    "text_final_bwd": [c_vp, c_vp, c_f, c_vp, c_vp, c_f, c_int, c_vp, c_vp, c_vp, c_f, c_int, c_vp, c_vp, c_vp,
-                       c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp],
-    "cast_f32_f16": [c_vp, c_vp, c_ll, c_vp],
-    "comm_unique_id": [c_vp],
-    "comm_init": [c_vp, c_int, c_int, C.POINTER(c_vp)],
-    "allreduce_flat": [c_vp, c_vp, c_ll, c_vp],
-    "comm_destroy": [c_vp],
-    "mapper_inputs": [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_vp],
-    "stream_create_cu_mask": [C.POINTER(C.c_uint), c_int, C.POINTER(c_vp)],
-    "stream_get_cu_mask": [c_vp, C.POINTER(C.c_uint), c_int],
-    "stream_destroy": [c_vp],
-    "lpips_prep": [c_vp, c_ll, c_ll, c_ll, c_ll, c_vp, c_int, c_int, c_int, c_vp],
-    "relu_f16": [c_vp, c_ll, c_vp],
-    "relu_maxpool2x2_f16": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp],
-    "lpips_distance": [c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int, c_vp, c_ll, c_vp, c_int, c_vp],
-}
-
-INT_FUNCS = {"gemm_select_tile": [c_int] * 3, "gemm_select_split": [c_int] * 5 + [c_ll],
-             "img_resample_ksize": [c_int] * 3}
-
-LL_FUNCS = {
-    "mapper_num_params": [c_int] * 4,
-    "mapper_save_floats": [c_int] * 3,
-    "mapper_rowgrad_floats": [c_int] * 4,
-    "mapper_legacy_input_params": [c_int] * 2,
-    "lpips_ws_floats": [c_int] * 3,
-}
-
-
-def call_ll(name: str, *args) -> int:
-    """call a `long long vneti_<name>(...)` size query; negative means unsupported."""
-    fn = getattr(load(), "vneti_" + name)
-    fn.argtypes = LL_FUNCS[name]
-    fn.restype = c_ll
-    return int(fn(*args))
+def query(name: str, *args) -> int:
+    """Call one of VALUE_FUNCS and return its number (a size query answers negative for an unsupported shape)."""
+    if name not in VALUE_FUNCS:
+        raise KeyError(f"vneti_{name} returns a status: use call()")
+    return int(getattr(load(), "vneti_" + name)(*args))

@@ -88,8 +88,7 @@ def gemm(A, B, out, *, bias=None, rowadd=None, rows_per_group=1, resid=None, alp
         d.workspace = ws.data_ptr()
         d.workspace_bytes = ws.numel() * ws.element_size()
     d.split_k = split_k if ws is not None else 1
-    rc = _l.load().vneti_gemm_f16(C.byref(d), stream())
-    _l.check(rc, "gemm_f16")
+    _l.call("gemm_f16", C.byref(d), stream())
 
 
 def im2col3x3_small(x, out, Bn, Cc, Hi, Wi, Ho, Wo, stride, pad_t, pad_l, strides):
@@ -113,20 +112,19 @@ def transpose(inp, out, rows, cols, batch, ld_in, stride_in, ld_out, stride_out)
 
 def transpose_multi(items):
     """items: up to 4 tuples with the arguments of `transpose`; one launch for all of them."""
-    import ctypes
     arr = (_l.TransposeDesc * len(items))()
     for d, (inp, out, rows, cols, batch, ld_in, stride_in, ld_out, stride_out) in zip(arr, items):
         d.inp, d.ld_in, d.stride_in = _p(inp), ld_in, stride_in
         d.out, d.ld_out, d.stride_out = _p(out), ld_out, stride_out
         d.rows, d.cols, d.batch = rows, cols, batch
-    _l.call("transpose_f16_multi", ctypes.addressof(arr), len(items), stream())
+    _l.call("transpose_f16_multi", arr, len(items), stream())
 
 
 def groupnorm_ws_floats(Bn, HW, Cc, G):
-    n = _l.load().vneti_groupnorm_ws_floats(Bn, HW, Cc, G)
+    n = _l.query("groupnorm_ws_floats", Bn, HW, Cc, G)
     if n < 0:
         raise RuntimeError(f"groupnorm: unsupported shape {(Bn, HW, Cc, G)}")
-    return int(n)
+    return n
 
 
 def groupnorm_fwd(x, y, gamma, beta, mean, rstd, ws, Bn, HW, Cc, G, eps, silu):
@@ -347,15 +345,15 @@ def nested_dropout_mask(mask, nl, Bn, hidden, prob, state, stream_id):
 
 
 def mapper_num_params(enc_dim, hidden, D, has_bypass=True):
-    return _l.call_ll("mapper_num_params", enc_dim, hidden, D, 1 if has_bypass else 0)
+    return _l.query("mapper_num_params", enc_dim, hidden, D, 1 if has_bypass else 0)
 
 
 def mapper_save_floats(R, enc_dim, hidden):
-    return _l.call_ll("mapper_save_floats", R, enc_dim, hidden)
+    return _l.query("mapper_save_floats", R, enc_dim, hidden)
 
 
 def mapper_rowgrad_floats(R, hidden, D, has_bypass=True):
-    return _l.call_ll("mapper_rowgrad_floats", R, hidden, D, 1 if has_bypass else 0)
+    return _l.query("mapper_rowgrad_floats", R, hidden, D, 1 if has_bypass else 0)
 
 
 def mapper_fwd(params, data, w_enc, hidden_mask, norm_scale, word, bypass, save, R, enc_dim, hidden, D, has_bypass,
@@ -383,7 +381,7 @@ def mapper_bwd(params, hidden_mask, norm_scale, word, dword_src, dword_rows, ld_
 
 
 def mapper_legacy_input_params(enc_dim, pe_dim):
-    return _l.call_ll("mapper_legacy_input_params", enc_dim, pe_dim)
+    return _l.query("mapper_legacy_input_params", enc_dim, pe_dim)
 
 
 def mapper_legacy_input_fwd(params_in, timesteps, w_pe, enc_out, nl, Bn, enc_dim, pe_dim, slot=None, slot_stride=0):
@@ -432,15 +430,11 @@ def mapper_inputs(timesteps, view_params, data, nl, Bn):
 
 
 def gemm_select_split(M, N, K, batch, tile_hint, workspace_bytes):
-    fn = _l.load().vneti_gemm_select_split
-    fn.argtypes = _l.INT_FUNCS["gemm_select_split"]
-    return int(fn(M, N, K, batch, tile_hint, workspace_bytes))
+    return _l.query("gemm_select_split", M, N, K, batch, tile_hint, workspace_bytes)
 
 
 def gemm_select_tile(M, N, batch=1):
-    fn = _l.load().vneti_gemm_select_tile
-    fn.argtypes = _l.INT_FUNCS["gemm_select_tile"]
-    return int(fn(M, N, batch))
+    return _l.query("gemm_select_tile", M, N, batch)
 
 
 # ------------------------------------------------------------------ LPIPS-VGG glue (csrc/lpips.hip)
@@ -465,7 +459,7 @@ def relu_maxpool2x2(x, out, Bn, H, W, Cc):
 
 
 def lpips_ws_floats(P, Cc, HW):
-    n = _l.call_ll("lpips_ws_floats", P, Cc, HW)
+    n = _l.query("lpips_ws_floats", P, Cc, HW)
     if n < 0:
         raise RuntimeError(f"lpips_distance: unsupported shape P={P} C={Cc} HW={HW}")
     return n
@@ -483,9 +477,7 @@ def lpips_distance(feat, n_img, pairs, w, Cc, HW, ws, out, accumulate=False):
 
 # ------------------------------------------------------------------ device-side input pipeline (csrc/image.hip)
 def img_resample_ksize(in_size, out_size, filt):
-    fn = _l.load().vneti_img_resample_ksize
-    fn.argtypes = _l.INT_FUNCS["img_resample_ksize"]
-    return int(fn(in_size, out_size, filt))
+    return _l.query("img_resample_ksize", in_size, out_size, filt)
 
 
 def img_resample_coeffs(in_size, out_size, filt, bounds, kk):
