@@ -27,9 +27,11 @@ def fixseed(seed: int):
 
 def prepare_directories(cfg):
     cfg.log.exp_dir = cfg.log.exp_dir / cfg.log.exp_name
-    if os.path.exists(cfg.log.exp_dir) and not cfg.log.overwrite_ok:
+    # log.auto_resume (extension): an existing folder is the run to continue — a pre-empted job relaunched with the same
+    # command line picks up at its newest complete trainer state (or starts fresh when there is none yet)
+    if os.path.exists(cfg.log.exp_dir) and not cfg.log.overwrite_ok and not cfg.log.auto_resume:
         raise ValueError(f"Experiment folder already exists and overwrite_ok=False: [{cfg.log.exp_dir}] "
-                         f"to overwrite the old experiment, add --log.overwrite_ok")
+                         f"to overwrite the old experiment, add --log.overwrite_ok (or --log.auto_resume to continue it)")
     cfg.log.logging_dir = cfg.log.exp_dir / cfg.log.logging_dir
 
 

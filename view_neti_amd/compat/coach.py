@@ -15,6 +15,10 @@ What is mirrored (file:line of the reference):
   * train loop, save every log.save_steps + final, file names            coach.py:137-274
   * validation images every eval.validation_steps (compat/validate.py: the live mappers on the inference engine;
     the DTU metric harness itself stays out of scope)                     coach.py:243-251, validate.py
+  * model.mapper_checkpoint_path: the reference's unfinished resume branch (coach.py:500-506 raises NotImplementedError,
+    "we don't save the optimizer"), delivered: with log.save_trainer_state the whole trainer state is written beside the
+    mapper checkpoints and a resumed run is bit-identical to the uninterrupted one; without a state file it is the warm
+    start the reference's comment describes (compat/resume.py)
 What differs on purpose: DESIGN.md §5 (no embedding restore, device RNG, flat-bucket all-reduce).
 """
 from __future__ import annotations
@@ -32,6 +36,7 @@ from .. import sd_config as sc
 from ..engine.step import TrainStepEngine
 from ..engine.text import unflatten_mapper_state
 from . import config as cfgmod
+from . import resume
 from .checkpoint_handler import CheckpointHandler
 from .constants import UNET_LAYERS
 from .dataset import TextualInversionDataset
@@ -58,6 +63,7 @@ class Coach:
         self.rank, self.world, self.local_rank = parallel.world_info()
         self.device = device
         self._setup_logging()
+        self._plan_resume()
         if cfg.optim.seed is not None:
             torch.manual_seed(cfg.optim.seed)
         if cfg.optim.mixed_precision not in ("fp16", "bf16"):
@@ -76,6 +82,8 @@ class Coach:
         self.sd = _sd_family(cfg)
         self.tokenizer = load_tokenizer(str(cfg.model.pretrained_model_name_or_path), self.sd.clip.vocab_size)
         self.train_dataset = self._init_dataset()
+        if self._trainer_state is not None:  # before the engines are built: a mismatch should not cost their set-up time
+            resume.check_fingerprint(self._trainer_state["fingerprint"], self._fingerprint())
         self._add_concept_tokens()
         unet_w, vae_w, clip_w, synthetic = load_sd_weights(self.sd, str(cfg.model.pretrained_model_name_or_path), device,
                                                            allow_synthetic=cfg.model.allow_synthetic_weights)
@@ -86,6 +94,8 @@ class Coach:
                      "this run are marked synthetic")
         clip_w = self._extend_token_embedding(clip_w)
         self.mapper_object_lookup, self.mapper_view = self._init_neti_mappers()
+        if self._resume_dir is not None:
+            self._load_resume_mappers()
         # engine slot k <-> k-th placeholder object token (mapper_object_lookup, coach.py:505-552)
         self.object_slot = {tid: k for k, tid in enumerate(self.placeholder_object_token_ids)}
         objs = [self.mapper_object_lookup[tid] for tid in self.placeholder_object_token_ids] \
@@ -114,7 +124,10 @@ class Coach:
             unconstrained_object=m.bypass_unconstrained_object, unconstrained_view=m.bypass_unconstrained_view,
             nested_dropout_prob=m.nested_dropout_prob if m.use_nested_dropout else 0.0,
             moment_cache_images=self._moment_cache_size(), **first.engine_encoder_kwargs(), **kw)
-        self.engine.set_lr(self.lr_schedule.lr(0))
+        if self._trainer_state is not None:
+            resume.check_fingerprint(self._trainer_state["fingerprint"], self._fingerprint(self.engine.params.numel()))
+            self.engine.load_state_dict(self._trainer_state.pop("engine"))
+        self.engine.set_lr(self.lr_schedule.lr(self.start_step))
         self.validator = None
         if cfg.eval.validation_prompts is not None and cfg.eval.validation_steps <= cfg.optim.max_train_steps \
                 and self.rank == 0:
@@ -134,15 +147,111 @@ class Coach:
         if self.world > 1:
             gen = torch.Generator()
             gen.manual_seed(parallel.data_seed(cfg.seed, self.rank))
-        self.train_dataloader = torch.utils.data.DataLoader(self.train_dataset, batch_size=bs, shuffle=True,
-                                                            num_workers=cfg.data.dataloader_num_workers,
-                                                            drop_last=True, generator=gen,
+        # the batches of DataLoader(shuffle=True, drop_last=True), draw for draw, from a sampler that keeps the epoch's
+        # permutation and the position in it where a trainer state can save them (compat/resume.py)
+        self._loader_generator = gen
+        self.batch_sampler = resume.ResumableBatchSampler(len(self.train_dataset), bs, generator=gen)
+        self.train_dataloader = torch.utils.data.DataLoader(self.train_dataset, batch_sampler=self.batch_sampler,
+                                                            num_workers=cfg.data.dataloader_num_workers, generator=gen,
                                                             collate_fn=TextualInversionDataset.collate)
         self.device_pipe, self._device_sources = None, {}
         if getattr(cfg.data, "device_input_pipeline", False):
             from ..engine.input_pipeline import DeviceImagePipeline
             _, _, ph, pw = self.engine.pixel_values.shape
             self.device_pipe = DeviceImagePipeline(ph, pw, device)
+
+    # ------------------------------------------------------------------ resumable training
+    def _plan_resume(self):
+        """Where this run starts, decided before anything is built: `log.auto_resume` (the newest complete state in
+        exp_dir, if there is one — a pre-empted job relaunched with the same command line) comes before
+        `model.mapper_checkpoint_path`.  A trainer state beside the mapper checkpoints makes it an EXACT resume, and its
+        autotuner picks are pinned now, before the engines tune; without one it is a warm start."""
+        cfg = self.cfg
+        self.start_step, self._resume_dir, self._trainer_state = 0, None, None
+        workers = cfg.data.dataloader_num_workers
+        no_workers = ("data.dataloader_num_workers must be 0 (is {}): the augmentation and caption draws must come from the "
+                      "streams the trainer state holds, not from worker processes").format(workers)
+        if cfg.log.save_trainer_state and workers > 0:
+            raise ValueError("log.save_trainer_state: " + no_workers)
+        src = None
+        if cfg.log.auto_resume:
+            n = resume.latest_complete_state(cfg.log.exp_dir, cfg.learnable_mode, self.world)
+            if n is not None:
+                src = (Path(cfg.log.exp_dir), n)
+            else:
+                self.log(f"log.auto_resume: no complete trainer state in {cfg.log.exp_dir}")
+        if src is None and cfg.model.mapper_checkpoint_path is not None:
+            src = resume.resolve_checkpoint(cfg.model.mapper_checkpoint_path, cfg.learnable_mode)
+        if src is None:
+            return
+        self._resume_dir, self.start_step = src
+        stem = self._resume_dir / f"mapper-steps-{self.start_step}"
+        sf = resume.state_file(self._resume_dir, self.start_step)
+        if not sf.is_file():
+            self.log(f"WARNING: warm start from {stem}: no {sf.name} beside it, so the AdamW moments and step counts are "
+                     "zero, the loss scale is at its initial value and the RNG streams are fresh — the mappers, the step "
+                     "count and the learning-rate schedule continue, the run is NOT the one that was interrupted")
+            return
+        if workers > 0:
+            raise ValueError(f"resuming from {sf}: " + no_workers)
+        state = resume.load_state(sf)
+        if self.rank > 0:
+            # the tensors are replicated after the all-reduce; what a rank owns is its host streams and its device RNG
+            own = resume.load_state(resume.state_file(self._resume_dir, self.start_step, self.rank))
+            state["host"] = own["host"]
+            state["engine"]["rng_state"] = own["rng_state"]
+        self._trainer_state = state
+        from ..engine.schedule import preload_picks
+        if preload_picks(state["picks"]):
+            self.log(f"exact resume from {stem} ({len(state['picks']['picks'])} autotuner picks pinned)")
+        else:
+            self.log(f"resume from {stem}: the kernel sources changed since the state was saved (kernel tree "
+                     f"{state['picks'].get('kernel_tree_sha')}), so the GEMM picks are tuned afresh — the continuation is "
+                     "exact in state but not bit-identical in arithmetic")
+
+    def _fingerprint(self, n_params: Optional[int] = None):
+        cfg = self.cfg
+        return resume.fingerprint(cfg.learnable_mode, cfg.optim.train_batch_size, cfg.optim.gradient_accumulation_steps,
+                                  self.world, cfg.optim.mixed_precision, cfg.seed, len(self.train_dataset), n_params)
+
+    def _load_resume_mappers(self):
+        """the mappers this run TRAINS take their weights from the checkpoint pair (a frozen view mapper, modes 4 / 5,
+        still comes from model.pretrained_view_mapper); flags such as the bypass alpha stay this run's"""
+        files = resume.mapper_files(self._resume_dir, self.start_step, self.cfg.learnable_mode)
+
+        def adopt(dst: NeTIMapper, src: NeTIMapper):
+            dst.load_state_dict(src.mapper_state(), strict=False)  # (load_mapper has checked the key set)
+            if dst.legacy:  # unseeded frequencies: the pickled encoder is their only record
+                dst.encoder.w = src.encoder.w.clone()
+
+        if "object" in files:
+            _, loaded = CheckpointHandler.load_mapper(files["object"], "object", self.train_dataset.placeholder_object_tokens,
+                                                      self.placeholder_object_token_ids)
+            if set(loaded) != set(self.mapper_object_lookup):
+                raise ValueError(f"{files['object']} holds object mappers for token ids {sorted(loaded)}, this run trains "
+                                 f"{sorted(self.mapper_object_lookup)}")
+            for tid, m in self.mapper_object_lookup.items():
+                adopt(m, loaded[tid])
+        if "view" in files:
+            _, view = CheckpointHandler.load_mapper(files["view"], "view", cam_mins=self.mapper_view.cam_mins,
+                                                    cam_maxs=self.mapper_view.cam_maxs)
+            adopt(self.mapper_view, view)
+
+    def save_trainer_state(self, step: int):
+        """`trainer-state-steps-N.pt`: the state of the loop about to draw the batch of step N + 1.  Rank 0 writes the
+        engine state, the picks, the fingerprint and its host streams; every other rank its own host streams and device
+        RNG state only."""
+        out = Path(self.cfg.log.exp_dir)
+        host = resume.capture_host_state(self.batch_sampler, self.train_dataset, self._loader_generator)
+        if self.rank > 0:
+            resume.atomic_save({"format": resume.FORMAT, "step": step, "host": host,
+                                "rng_state": self.engine.rng_state.cpu()}, resume.state_file(out, step, self.rank))
+            return
+        from ..engine.schedule import export_picks
+        resume.atomic_save({"format": resume.FORMAT, "step": step, "engine": self.engine.state_dict(),
+                            "picks": export_picks(), "fingerprint": self._fingerprint(self.engine.params.numel()),
+                            "host": host}, resume.state_file(out, step))
+        resume.prune_states(out, self.cfg.log.keep_trainer_states)
 
     def _moment_cache_size(self) -> int:
         """`data.cache_vae_moments` (extension): legal only where the pixels of dataset item i are the same
@@ -354,15 +463,25 @@ class Coach:
                      f"  Gradient Accumulation steps = {cfg.optim.gradient_accumulation_steps}",
                      f"  Total optimization steps = {cfg.optim.max_train_steps}"):
             self.log(line)
-        global_step, captured, t0 = 0, False, time.time()
+        global_step, captured, t0 = self.start_step, False, time.time()
+        if self.start_step:
+            self.log(f"  Continuing after optimization step {self.start_step}")
         if cfg.learnable_mode == 3:
             # every rank must draw the same scene each step (one all-reduce of that scene's mapper); the
             # reference leaves np.random unseeded per process, which only works because its DDP wrapper never
             # sees the dict-held object mappers
             import numpy as np
             np.random.seed(cfg.seed if cfg.seed is not None else 0)
+        # exact resume: the saved host streams go back in AFTER the seeding above, after everything __init__ drew and
+        # after the loader's iterator drew its base seed — the sampler then continues the saved epoch without a draw
+        host = self._trainer_state["host"] if self._trainer_state is not None else None
+        self._trainer_state = None
         while global_step < cfg.optim.max_train_steps:
-            for batch in self.train_dataloader:
+            batches = iter(self.train_dataloader)
+            if host is not None:
+                resume.restore_host_state(host, self.batch_sampler, self.train_dataset, self._loader_generator)
+                host = None
+            for batch in batches:
                 ids_obj = batch["input_ids_placeholder_object"]
                 if not bool((ids_obj == ids_obj[0]).all()):
                     raise ValueError("a batch must hold a single object token (net_clip_text_embedding.py:67-68)")
@@ -382,11 +501,13 @@ class Coach:
                         eng.set_lr(self.lr_schedule.lr(global_step))  # device scalar: no re-capture
                     if global_step % 50 == 0 or global_step == 1:
                         self.log(f"step {global_step} loss {eng.loss():.5f} lr {float(eng.hyper[0]):.2e} "
-                                 f"{global_step / (time.time() - t0):.2f} it/s")
+                                 f"{(global_step - self.start_step) / (time.time() - t0):.2f} it/s")
                     if global_step % cfg.log.save_steps == 0:
                         self.save(f"learned_embeds-steps-{global_step}.bin", f"mapper-steps-{global_step}.pt")
                     if self.validator is not None and global_step % cfg.eval.validation_steps == 0:  # coach.py:243,834
                         self.validator.infer(global_step)
+                    if cfg.log.save_trainer_state and global_step % cfg.log.save_steps == 0:
+                        self.save_trainer_state(global_step)  # after the mapper save AND the validation of this step
                 if global_step >= cfg.optim.max_train_steps:
                     break
         torch.cuda.synchronize()

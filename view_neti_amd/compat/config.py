@@ -42,6 +42,18 @@ class LogConfig:
     report_to: str = "all"
     checkpoints_total_limit: Optional[int] = None
     save_dataset_images: bool = True
+    # extensions (not in the reference, which saves mappers only and never finished its resume branch, coach.py:500-506):
+    # `trainer-state-steps-N.pt` beside the mapper checkpoints of every `save_steps` — AdamW moments, step counts, loss
+    # scale, device and host RNG streams, position in the shuffled epoch — from which `model.mapper_checkpoint_path` /
+    # `auto_resume` continue bit-identically (compat/resume.py).  All off by default.  They are run control
+    # ("run_control": True): they say how a process was launched, not what it trained, so a checkpoint's `vneti_ext` never
+    # holds them, and config.yaml names them only where they are set — a run that does not use them writes the file it
+    # always wrote
+    save_trainer_state: bool = field(default=False, metadata={"ext": True, "run_control": True})
+    # newest K states stay on disk (0 = all)
+    keep_trainer_states: int = field(default=2, metadata={"ext": True, "run_control": True})
+    # continue from the newest complete state in exp_dir
+    auto_resume: bool = field(default=False, metadata={"ext": True, "run_control": True})
 
 
 @dataclass
@@ -221,10 +233,11 @@ def encode(obj, include_ext: bool = True):
     """pyrallis.encode: dataclass -> plain dict (Path -> str), used for config.yaml and inside checkpoints
     (training/logger.py:25-28, checkpoint_handler.py:59,64).  `include_ext=False` leaves out the fields this repo
     adds to the reference's schema (metadata ext=True): the reference's `pyrallis.decode(RunConfig, ckpt['cfg'])`
-    (checkpoint_handler.py:142) rejects keys it does not know."""
+    (checkpoint_handler.py:142) rejects keys it does not know.  Run-control extensions appear only where they are set."""
     if is_dataclass(obj) and not isinstance(obj, type):
         return {f.name: encode(getattr(obj, f.name), include_ext) for f in fields(obj)
-                if include_ext or not f.metadata.get("ext")}
+                if (include_ext or not f.metadata.get("ext"))
+                and not (f.metadata.get("run_control") and getattr(obj, f.name) == f.default)}
     if isinstance(obj, Path):
         return str(obj)
     if isinstance(obj, dict):
@@ -235,13 +248,14 @@ def encode(obj, include_ext: bool = True):
 
 
 def ext_fields(obj) -> Dict[str, Any]:
-    """{"section.field": value} of the extension fields (stored beside, not inside, a checkpoint's cfg)."""
+    """{"section.field": value} of the extension fields that describe the trained model or its data (stored beside, not
+    inside, a checkpoint's cfg); run-control extensions (metadata "run_control") stay out of checkpoints."""
     out = {}
     for f in fields(obj):
         v = getattr(obj, f.name)
         if is_dataclass(v):
             out.update({f"{f.name}.{k}": x for k, x in ext_fields(v).items()})
-        elif f.metadata.get("ext"):
+        elif f.metadata.get("ext") and not f.metadata.get("run_control"):
             out[f.name] = v
     return out
 

@@ -543,3 +543,26 @@ class Schedule:
 
     def backward(self):
         self._run(self.bwd)
+
+
+# ---------------------------------------------------------------------- the autotuner's picks as plain data
+def export_picks() -> Dict:
+    """the picks pinned so far in this process, in the repr-keyed form of the VNETI_AUTOTUNE_CACHE JSON, stamped with the
+    kernel tree they were timed on.  A trainer state carries them: two engines compute bit-identical steps only with the
+    same tile / split-K / K-order per GEMM, and picks are TIMED, so a second process may pin others."""
+    from ..roofline import kernel_tree_sha
+    return {"kernel_tree_sha": kernel_tree_sha(),
+            "picks": {repr(k): [int(x) for x in v] for k, v in Schedule._tile_cache.items()}}
+
+
+def preload_picks(data: Dict) -> bool:
+    """pin exported picks before any engine is built (engines built afterwards find their problems in the cache and time
+    nothing).  Picks timed on another kernel tree are refused — nothing is loaded, False is returned — and the caller's
+    engines tune afresh."""
+    import ast
+    from ..roofline import kernel_tree_sha
+    if data.get("kernel_tree_sha") != kernel_tree_sha():
+        return False
+    for k, v in data["picks"].items():
+        Schedule._tile_cache[ast.literal_eval(k)] = tuple(int(x) for x in v)
+    return True

@@ -238,6 +238,44 @@ class TrainStepEngine:
         st.upload("lr", self.hyper[0:1], torch.tensor([lr], dtype=torch.float32))
         st.end()
 
+    # ------------------------------------------------------------------ trainer state (resumable training)
+    _STATE = ("params", "exp_avg", "exp_avg_sq", "opt_step", "seg_step", "scaler", "rng_state", "hyper")
+
+    def _describe(self) -> Dict:
+        from .. import lib
+        return {"n_params": self.params.numel(), "n_objects": self.n_objects, "n_obj": self.n_obj,
+                "view_in_bucket": self.params.numel() > self.n_all_obj, "grad_accum": self.grad_accum,
+                "world_size": self.world_size, "precision": lib.precision()}
+
+    def state_dict(self) -> Dict:
+        """CPU copies of everything the captured step reads and writes in place — the set `_capture` snapshots around its
+        warm-up, plus the hyper-parameters — and a description `load_state_dict` validates.  Gradients are not state: the
+        first micro-step of a group overwrites them.  The VAE moment cache is not state either (D14: a hit and a miss are
+        bit-identical)."""
+        if self.micro != 0:
+            raise RuntimeError(f"state_dict() inside a gradient-accumulation group (micro-step {self.micro} of "
+                               f"{self.grad_accum}): the accumulated gradients are not part of the state")
+        sd = {name: getattr(self, name).detach().cpu().clone() for name in self._STATE}
+        sd["meta"] = self._describe()
+        return sd
+
+    def load_state_dict(self, sd: Dict):
+        """copies IN PLACE (the captured graphs hold these buffers' addresses): valid before capture() — whose warm-up
+        snapshot then carries the loaded values — and after it, without re-capture.  `hyper` comes back as saved, lr
+        included; a caller with a schedule rewrites the lr through set_lr()."""
+        if self.micro != 0:
+            raise RuntimeError("load_state_dict() inside a gradient-accumulation group")
+        want, have = self._describe(), sd.get("meta", {})
+        bad = [f"{k}: saved {have.get(k)!r}, this engine {v!r}" for k, v in want.items() if have.get(k) != v]
+        bad += [f"{name}: saved shape {tuple(sd[name].shape) if name in sd else None}, this engine "
+                f"{tuple(getattr(self, name).shape)}" for name in self._STATE
+                if name not in sd or sd[name].shape != getattr(self, name).shape or sd[name].dtype != getattr(self, name).dtype]
+        if bad:
+            raise ValueError("trainer state does not fit this engine: " + "; ".join(bad))
+        for name in self._STATE:
+            getattr(self, name).copy_(sd[name])
+        torch.cuda.current_stream().synchronize()
+
     # ------------------------------------------------------------------ the step
     def forward_backward(self, accumulate: bool = False, cached: bool = False):
         """cached: the batch's VAE moments come out of the moment cache (no encoder launches); otherwise the encoder runs
