@@ -358,6 +358,15 @@ int vneti_image_postprocess(const void* img, long long ldi, float* out, long lon
 int vneti_mse_loss_grad(const void* pred, long long ldp, const float* target, void* dpred,
                         long long lddp, float* loss_sum, const float* loss_scale, int Bn, int Lc,
                         int HW, void* stream);
+/* F.mse_loss(pred.float(), target.float(), reduction="none").mean(dim=(1,2,3)): one loss per sample, forward only.  The
+ * held-out evaluation of a run (view_neti_amd/compat/heldout.py): the batch-mean form of training/coach.py:211 split by
+ * sample, so that a loss can be attributed to a camera the way training/validate.py:65-186 attributes its image metrics.
+ * Layouts as vneti_mse_loss_grad: pred 16-bit NHWC [Bn][HW][ldp] (ldp >= Lc), target f32 NCHW [Bn][Lc][HW]; out f32 [Bn].
+ * Deterministic (fixed-order two-stage reduction, no float atomics), and out[b] depends on sample b's data and (Lc, HW)
+ * only: not on Bn, not on b.  ws: vneti_mse_loss_per_sample_ws_floats(Bn, HW) floats of scratch (negative: bad shape). */
+int vneti_mse_loss_per_sample(const void* pred, long long ldp, const float* target, float* out, float* ws, int Bn, int Lc,
+                              int HW, void* stream);
+long long vneti_mse_loss_per_sample_ws_floats(int Bn, int HW);
 /* torch.optim.AdamW over one flat f32 bucket with torch.cuda.amp.GradScaler semantics
  * (training/coach.py:214-218,750-756).  hyper = {lr, beta1, beta2, eps, weight_decay, grad_div};
  * scaler = {loss_scale, growth_tracker, found_inf}; step = int32 optimizer step count.

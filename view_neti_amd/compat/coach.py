@@ -58,8 +58,12 @@ def _sd_family(cfg) -> sc.SDConfig:
 
 
 class Coach:
-    def __init__(self, cfg: cfgmod.RunConfig, device: str = "cuda"):
+    def __init__(self, cfg: cfgmod.RunConfig, device: str = "cuda", forward_only: bool = False):
+        """forward_only: the set-up of a run without its training side, for evaluating saved checkpoints
+        (compat/heldout.py::offline) — the same dataset, tokenizer, mappers and engine inputs, an engine without backward
+        schedules, no resume, no validator, and nothing written to exp_dir but what the caller writes."""
         self.cfg = cfg
+        self.forward_only = forward_only
         self.rank, self.world, self.local_rank = parallel.world_info()
         self.device = device
         self._setup_logging()
@@ -123,20 +127,26 @@ class Coach:
             grad_accum=cfg.optim.gradient_accumulation_steps, hidden_object=first.hidden,
             unconstrained_object=m.bypass_unconstrained_object, unconstrained_view=m.bypass_unconstrained_view,
             nested_dropout_prob=m.nested_dropout_prob if m.use_nested_dropout else 0.0,
-            moment_cache_images=self._moment_cache_size(), **first.engine_encoder_kwargs(), **kw)
+            moment_cache_images=0 if forward_only else self._moment_cache_size(), need_backward=not forward_only,
+            **first.engine_encoder_kwargs(), **kw)
         if self._trainer_state is not None:
             resume.check_fingerprint(self._trainer_state["fingerprint"], self._fingerprint(self.engine.params.numel()))
             self.engine.load_state_dict(self._trainer_state.pop("engine"))
         self.engine.set_lr(self.lr_schedule.lr(self.start_step))
         self.validator = None
         if cfg.eval.validation_prompts is not None and cfg.eval.validation_steps <= cfg.optim.max_train_steps \
-                and self.rank == 0:
+                and self.rank == 0 and not forward_only:
             from .sd_weights import load_vae_decoder_weights
             from .validate import ValidationHandler
             dec_w, _ = load_vae_decoder_weights(self.sd, str(cfg.model.pretrained_model_name_or_path), device,
                                                 allow_synthetic=cfg.model.allow_synthetic_weights)
             self.validator = ValidationHandler(self, unet_w, dec_w, clip_w)
         del unet_w, vae_w, clip_w
+        # held-out diffusion loss (extension): rank 0, like the validator; a missing evaluation image raises here
+        self.heldout = None
+        if cfg.eval.heldout_loss_steps > 0 and self.rank == 0 and not forward_only:
+            from .heldout import HeldoutLoss
+            self.heldout = HeldoutLoss(self)
         self.checkpoint_handler = CheckpointHandler(
             cfg, self.train_dataset.placeholder_view_tokens, self.placeholder_view_token_ids,
             self.train_dataset.placeholder_object_tokens, self.placeholder_object_token_ids, cfg.log.exp_dir,
@@ -168,6 +178,8 @@ class Coach:
         autotuner picks are pinned now, before the engines tune; without one it is a warm start."""
         cfg = self.cfg
         self.start_step, self._resume_dir, self._trainer_state = 0, None, None
+        if self.forward_only:
+            return
         workers = cfg.data.dataloader_num_workers
         no_workers = ("data.dataloader_num_workers must be 0 (is {}): the augmentation and caption draws must come from the "
                       "streams the trainer state holds, not from worker processes").format(workers)
@@ -214,10 +226,11 @@ class Coach:
         return resume.fingerprint(cfg.learnable_mode, cfg.optim.train_batch_size, cfg.optim.gradient_accumulation_steps,
                                   self.world, cfg.optim.mixed_precision, cfg.seed, len(self.train_dataset), n_params)
 
-    def _load_resume_mappers(self):
+    def _load_resume_mappers(self, directory=None, step: Optional[int] = None):
         """the mappers this run TRAINS take their weights from the checkpoint pair (a frozen view mapper, modes 4 / 5,
         still comes from model.pretrained_view_mapper); flags such as the bypass alpha stay this run's"""
-        files = resume.mapper_files(self._resume_dir, self.start_step, self.cfg.learnable_mode)
+        files = resume.mapper_files(self._resume_dir if directory is None else directory,
+                                    self.start_step if step is None else step, self.cfg.learnable_mode)
 
         def adopt(dst: NeTIMapper, src: NeTIMapper):
             dst.load_state_dict(src.mapper_state(), strict=False)  # (load_mapper has checked the key set)
@@ -236,6 +249,21 @@ class Coach:
             _, view = CheckpointHandler.load_mapper(files["view"], "view", cam_mins=self.mapper_view.cam_mins,
                                                     cam_maxs=self.mapper_view.cam_maxs)
             adopt(self.mapper_view, view)
+
+    def load_mappers(self, directory, step: int):
+        """`mapper-steps-{step}` of `directory` into the modules and, IN PLACE, into the engine's bucket (the captured
+        graphs keep reading the same addresses) — the inverse of _sync_modules"""
+        from ..engine.text import flatten_mapper_state
+        missing = [str(f) for f in resume.mapper_files(directory, step, self.cfg.learnable_mode).values() if not f.is_file()]
+        if missing:
+            raise FileNotFoundError(f"iteration {step}: missing {missing}")
+        self._load_resume_mappers(directory, step)
+        eng = self.engine
+        for tid, k in self.object_slot.items():
+            eng.object_params(k).copy_(flatten_mapper_state(self.mapper_object_lookup[tid].mapper_state()))
+        if self.mapper_view is not None and eng.view_params_flat().numel() > 0:
+            eng.view_params_flat().copy_(flatten_mapper_state(self.mapper_view.mapper_state()))
+        torch.cuda.current_stream().synchronize()
 
     def save_trainer_state(self, step: int):
         """`trainer-state-steps-N.pt`: the state of the loop about to draw the batch of step N + 1.  Rank 0 writes the
@@ -285,7 +313,11 @@ class Coach:
         self.logger = logging.getLogger(f"vneti.coach.{id(self)}")
         self.logger.setLevel(logging.INFO)
         fmt = logging.Formatter("%(asctime)s %(message)s", "%Y-%m-%d %H:%M:%S")
-        if self.rank == 0:
+        if self.rank == 0 and self.forward_only:
+            h = logging.StreamHandler(sys.stdout)
+            h.setFormatter(fmt)
+            self.logger.addHandler(h)
+        elif self.rank == 0:
             cfg.log.exp_dir.mkdir(parents=True, exist_ok=True)
             cfg.log.logging_dir.mkdir(parents=True, exist_ok=True)
             for h in (logging.StreamHandler(sys.stdout), logging.FileHandler(cfg.log.logging_dir / "log.txt")):
@@ -504,6 +536,9 @@ class Coach:
                                  f"{(global_step - self.start_step) / (time.time() - t0):.2f} it/s")
                     if global_step % cfg.log.save_steps == 0:
                         self.save(f"learned_embeds-steps-{global_step}.bin", f"mapper-steps-{global_step}.pt")
+                    if self.heldout is not None and (global_step % cfg.eval.heldout_loss_steps == 0
+                                                     or global_step == cfg.optim.max_train_steps):
+                        self.heldout.run(global_step)  # before the validation and the trainer-state save of this step
                     if self.validator is not None and global_step % cfg.eval.validation_steps == 0:  # coach.py:243,834
                         self.validator.infer(global_step)
                     if cfg.log.save_trainer_state and global_step % cfg.log.save_steps == 0:

@@ -168,6 +168,21 @@ class EvalConfig:
     num_denoising_steps: int = 30
     dtu_upsample_key: int = 1
     eval_placeholder_object_tokens: List[str] = None
+    # extensions (not in the reference), all off by default and run control like log.save_trainer_state: they
+    # say how a run is watched, not what it trained.
+    # held-out diffusion loss (compat/heldout.py): every N optimizer steps and at the last one, the forward half of the
+    # train step on the 34 DTU evaluation views at K fixed timesteps t_k = floor((2k+1) T / (2K)) with fixed noise
+    # (generator seed = heldout_loss_seed + 1000 * camera + k), split into train / test cameras -> heldout-loss.jsonl
+    heldout_loss_steps: int = field(default=0, metadata={"ext": True, "run_control": True})
+    heldout_loss_timesteps: int = field(default=4, metadata={"ext": True, "run_control": True})
+    heldout_loss_seed: int = field(default=0, metadata={"ext": True, "run_control": True})
+    # the reference's validation (training/validate.py:65-186): render the 34 evaluation views x validation_seeds at the
+    # novel-view resolution, `validation_nvs_batch` prompts per sampler run, and score them against the scene
+    validation_nvs: bool = field(default=False, metadata={"ext": True, "run_control": True})
+    validation_nvs_batch: int = field(default=4, metadata={"ext": True, "run_control": True})
+    # LPIPS(net="vgg") for that scoring (compat/lpips.py; fp16 runs only): torchvision's vgg16 and lpips' linear heads
+    lpips_vgg_weights: Optional[Path] = field(default=None, metadata={"ext": True, "run_control": True})
+    lpips_lin_weights: Optional[Path] = field(default=None, metadata={"ext": True, "run_control": True})
     # plain class attribute in the reference too (config.py:188)
     validation_view_tokens = None
 
@@ -176,6 +191,8 @@ class EvalConfig:
             self.validation_seeds = list(range(self.num_validation_images))
         assert len(self.validation_seeds) == self.num_validation_images, \
             "Length of validation_seeds should equal num_validation_images"
+        if self.heldout_loss_steps < 0 or self.heldout_loss_timesteps < 1 or self.validation_nvs_batch < 1:
+            raise ValueError("eval: heldout_loss_steps >= 0, heldout_loss_timesteps >= 1 and validation_nvs_batch >= 1")
 
 
 @dataclass

@@ -220,6 +220,16 @@ class TextualInversionDataset(torch.utils.data.Dataset):
             arr = np.concatenate([arr, np.zeros((400, arr.shape[1], 3), np.uint8)], 0)
         return arr
 
+    def load_pixels(self, path) -> torch.Tensor:
+        """the deterministic part of __getitem__'s image path — RGB, centre crop, `_resize`, [-1, 1] as (3, H, W) f32 —
+        without flip or augmentation and without a random draw (held-out evaluation, compat/heldout.py)"""
+        image = Image.open(path)
+        if image.mode != "RGB":
+            image = image.convert("RGB")
+        image = self._resize(Image.fromarray(self._source_array(image)))
+        arr = (np.array(image).astype(np.uint8) / 127.5 - 1.0).astype(np.float32)
+        return torch.from_numpy(arr).permute(2, 0, 1)
+
     @staticmethod
     def collate(samples):
         """default collation, except that the augmentation plans stay python objects"""

@@ -431,6 +431,47 @@ __global__ __launch_bounds__(256) void mse_loss_grad_kernel(const half_t* pred, 
   if (threadIdx.x == 0) atomicAdd(loss_sum, red[0] + red[1] + red[2] + red[3]);
 }
 
+// ---- per-sample MSE, forward only (held-out evaluation) -----------------------------------------
+// The same layouts as mse_loss_grad_kernel; out[b] = mean over (c, p) of (pred - target)^2 of sample b alone.  Two stages in a
+// FIXED order, no float atomics (as lpips_dist_kernel / lpips_dist_finish_kernel): block (chunk, b) owns the kMseChunk pixels
+// [chunk * kMseChunk, ...) of sample b — one pixel per thread, its Lc channels summed in channel order, then the LDS tree —
+// and writes ws[b * nchunk + chunk]; the finish adds a sample's partials in chunk order in f64.  The partition depends on
+// (Lc, HW) only, never on Bn or on b: a sample's value is bit-identical wherever it sits in whatever batch.  A non-finite
+// element poisons the partial of its own sample only.
+constexpr int kMseChunk = 256;
+__global__ __launch_bounds__(kMseChunk) void mse_per_sample_kernel(const half_t* __restrict__ pred, long long ldp,
+                                                                   const float* __restrict__ target, float* __restrict__ ws,
+                                                                   int Lc, int HW, int nchunk) {
+  __shared__ float red[kMseChunk];
+  const int b = blockIdx.y, chunk = blockIdx.x, t = threadIdx.x;
+  const int p = chunk * kMseChunk + t;
+  float acc = 0.f;
+  if (p < HW) {
+    const half_t* pr = pred + ((long long)b * HW + p) * ldp;
+    const float* tg = target + (long long)b * Lc * HW + p;
+    for (int c = 0; c < Lc; ++c) {
+      const float d = (float)pr[c] - tg[(long long)c * HW];
+      acc = fmaf(d, d, acc);
+    }
+  }
+  red[t] = acc;
+  __syncthreads();
+#pragma unroll
+  for (int s = kMseChunk / 2; s > 0; s >>= 1) {
+    if (t < s) red[t] += red[t + s];
+    __syncthreads();
+  }
+  if (t == 0) ws[(long long)b * nchunk + chunk] = red[0];
+}
+__global__ __launch_bounds__(256) void mse_per_sample_finish_kernel(const float* __restrict__ ws, int Bn, int nchunk,
+                                                                    double inv_n, float* __restrict__ out) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= Bn) return;
+  double s = 0.0;
+  for (int k = 0; k < nchunk; ++k) s += (double)ws[(long long)b * nchunk + k];
+  out[b] = (float)(s * inv_n);
+}
+
 // ---- AdamW over a flat f32 bucket with torch.cuda.amp.GradScaler semantics ---------------------
 // scaler[0] = loss scale, scaler[1] = growth tracker, scaler[2] = found_inf (this step),
 // hyper: lr, beta1, beta2, eps, weight_decay, grad_div (= world size for DP mean)
@@ -761,6 +802,27 @@ extern "C" int vneti_mse_loss_grad(const void* pred, long long ldp, const float*
   hipLaunchKernelGGL(mse_loss_grad_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ST, (const half_t*)pred, ldp, target,
                      (half_t*)dpred, lddp, loss_sum, loss_scale, Bn, Lc, HW);
   return vneti_check_launch("mse_loss_grad");
+}
+
+extern "C" long long vneti_mse_loss_per_sample_ws_floats(int Bn, int HW) {
+  if (Bn <= 0 || HW <= 0) return -1;
+  return (long long)Bn * cdiv(HW, kMseChunk);
+}
+
+extern "C" int vneti_mse_loss_per_sample(const void* pred, long long ldp, const float* target, float* out, float* ws,
+                                         int Bn, int Lc, int HW, void* stream) {
+  VN_REQUIRE(pred && target && out && ws, "mse_loss_per_sample: null pointer");
+  VN_REQUIRE(Bn > 0 && Bn <= 65535 && Lc > 0 && HW > 0 && ldp >= Lc,
+             "mse_loss_per_sample: bad shape Bn=%d Lc=%d HW=%d ldp=%lld (0 < Bn <= 65535, ldp >= Lc)", Bn, Lc, HW, ldp);
+  VN_REQUIRE((long long)Bn * Lc * HW < 0x7fffffffLL, "mse_loss_per_sample: Bn * Lc * HW over 2^31");
+  const int nchunk = cdiv(HW, kMseChunk);
+  hipLaunchKernelGGL(mse_per_sample_kernel, dim3(nchunk, Bn), dim3(kMseChunk), 0, ST, (const half_t*)pred, ldp, target, ws,
+                     Lc, HW, nchunk);
+  const int rc = vneti_check_launch("mse_loss_per_sample");
+  if (rc != VNETI_OK) return rc;
+  hipLaunchKernelGGL(mse_per_sample_finish_kernel, dim3(cdiv(Bn, 256)), dim3(256), 0, ST, (const float*)ws, Bn, nchunk,
+                     1.0 / ((double)Lc * (double)HW), out);
+  return vneti_check_launch("mse_loss_per_sample_finish");
 }
 
 extern "C" int vneti_adamw_segments(float* p, const float* g, float* m, float* v, long long seg_len, int n_seg,

@@ -173,6 +173,11 @@ class TrainStepEngine:
             self._batch_cached = False    # does the batch set by set_batch() consist of cached images only
             self._batch_images = ()
         self.graph_a_c = self.graph_acc_c = None  # the captured step without the VAE encoder (moments from the cache)
+        # held-out evaluation (eval_losses): per-sample losses and the scratch of their two-stage reduction
+        self.eval_out = torch.zeros(batch, dtype=torch.float32, device=device)
+        self.eval_ws = torch.zeros(ops.mse_loss_per_sample_ws_floats(batch, self.h * self.w), dtype=torch.float32,
+                                   device=device)
+        self.graph_eval = None
         from .staging import HostStager
         self.stager = HostStager()
         self.need_backward = need_backward
@@ -181,25 +186,32 @@ class TrainStepEngine:
         self.graph_a = self.graph_b = self.graph_acc = None
         self.exchange_in_graph = False
         self.micro = 0
+        self._eval_batch = False  # the current batch was set for eval_losses(): not to be trained on
         self.n_loss = batch * Lc * self.h * self.w
 
     # ------------------------------------------------------------------ inputs
     def set_batch(self, pixel_values, input_ids, placeholder_object, placeholder_view=None, view_params=None,
-                  object_index: int = 0, image_idx=None):
+                  object_index: int = 0, image_idx=None, for_eval: bool = False):
         """object_index: which object mapper this batch trains (a batch is single-scene:
-        models/net_clip_text_embedding.py:67-76 asserts one placeholder id and looks its mapper up)."""
+        models/net_clip_text_embedding.py:67-76 asserts one placeholder id and looks its mapper up).
+        for_eval: a batch for eval_losses(): its images are no dataset items, so the moment cache is neither consulted nor
+        told about them (image_idx is ignored).  Such a batch is not trained on: step() refuses until the next set_batch()
+        (with a cache, the encoder's moments would otherwise land in the slots of the previous training batch)."""
         if not 0 <= object_index < self.n_objects:
             raise ValueError(f"object_index {object_index} out of range (have {self.n_objects} object mappers)")
         if self.micro != 0 and object_index != self.active_object:
             raise ValueError("the object mapper may not change inside a gradient-accumulation group")
         self.active_object = object_index
         self.obj_slot.fill_(object_index)
+        self._eval_batch = bool(for_eval)
         # every host -> device upload of the batch goes through a pinned staging slot (engine/staging.py): the host does not
         # wait for the previous step's graph, it enqueues the copies behind it and moves on
         st = self.stager
         st.begin()
         try:
-            if self.n_cache:
+            if self.n_cache and for_eval:
+                self._batch_images, self._batch_cached = (), False  # no slot of the cache belongs to this batch
+            elif self.n_cache:
                 if image_idx is None:
                     raise ValueError("the moment cache needs the dataset index of every image of the batch (image_idx)")
                 ids = tuple(int(i) for i in image_idx)
@@ -337,6 +349,56 @@ class TrainStepEngine:
             ops.adamw_flat(*view, *a, phases=ops.OPT_APPLY)
         ops.adamw_segments(*obj, *a, phases=ops.OPT_APPLY | ops.OPT_FINISH)
 
+    # ------------------------------------------------------------------ held-out evaluation
+    def eval_forward(self):
+        """the forward half of the step on the batch of set_batch(..., for_eval=True) and the randomness of set_noise(): VAE
+        encoder -> sample_add_noise -> text pass in eval mode (no nested-dropout draw) -> UNet -> one MSE per sample into
+        eval_out.  A strict subset of forward_backward's launches plus the per-sample loss: it reads the trainable state and
+        writes activations only — no RNG advance, no loss_sum, no gradient, no optimizer, no moment-cache write."""
+        B, Lc, hw = self.B, self.cfg.vae.latent_channels, self.h * self.w
+        mode = self.text.training
+        self.text.training = False
+        try:
+            self.vae.forward()
+            ops.sample_add_noise(self.vae.moments, self.eps, self.noise, self.timesteps, self.ac,
+                                 self.cfg.vae.scaling_factor, self.cfg.ddpm.prediction_type == "v_prediction", self.latents,
+                                 self.unet.x_in, self.target, B, Lc, hw)
+            self.text.forward()
+            self.unet.forward_pre()
+            self.unet.forward_main()
+            ops.mse_loss_per_sample(self.unet.pred, self.target, self.eval_out, self.eval_ws, B, Lc, hw)
+        finally:
+            self.text.training = mode
+
+    def eval_losses(self, graph: bool = True) -> torch.Tensor:
+        """per-sample diffusion losses of the current batch, CPU float32 [B] (forces a device sync).  Legal between
+        optimizer steps only.  graph=True replays `graph_eval`, captured on first use (and again by capture());
+        graph=False launches eagerly."""
+        if self.micro != 0:
+            raise ValueError(f"eval_losses() inside a gradient-accumulation group (micro-step {self.micro} of "
+                             f"{self.grad_accum}): legal between optimizer steps only")
+        if not graph:
+            self.eval_forward()
+        else:
+            if self.graph_eval is None:
+                self._capture_eval()
+            self.graph_eval.replay()
+        return self.eval_out.cpu()
+
+    def _capture_eval(self):
+        """the warm-up launch is an evaluation itself: nothing to snapshot"""
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            self.eval_forward()
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=s):
+                self.eval_forward()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        self.graph_eval = g
+
     def all_reduce(self):
         """the one exchange step of data-parallel training: sum the mapper gradients over ranks
         (the 1/world_size is folded into AdamW).  With several object mappers every rank trains the
@@ -377,8 +439,14 @@ class TrainStepEngine:
             self._cached_images.difference_update(int(i) for i in image_idx)
         self._batch_cached = all(i in self._cached_images for i in self._batch_images) and bool(self._batch_images)
 
+    def _refuse_eval_batch(self):
+        if self._eval_batch:
+            raise RuntimeError("the current batch was set with for_eval=True (held-out evaluation): call set_batch() with a "
+                               "training batch before step()")
+
     def step_eager(self):
         """one micro-step; the optimizer runs after every `grad_accum`-th micro-step."""
+        self._refuse_eval_batch()
         cached = self._use_cache()
         self.forward_backward(accumulate=self.micro > 0, cached=cached)
         self._mark_cached(cached)
@@ -473,11 +541,15 @@ class TrainStepEngine:
                     self.optimizer_step()
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
+        if self.graph_eval is not None:  # captured before this (re-)capture: renew it with the others
+            self.graph_eval = None
+            self._capture_eval()
 
     def step(self) -> bool:
         """one micro-step (graph replay when captured); returns True when the optimizer stepped."""
         if self.graph_a is None:
             return self.step_eager()
+        self._refuse_eval_batch()
         if self.exchange_in_graph and getattr(self.exchange, "closed", False):
             raise RuntimeError("the step's graph holds a collective on an RCCL communicator that has been closed (process "
                                "group re-initialised?): rebuild the engine")

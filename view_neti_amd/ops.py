@@ -326,6 +326,20 @@ def mse_loss_grad(pred, target, dpred, loss_sum, loss_scale, Bn, Lc, HW):
             Bn, Lc, HW, stream())
 
 
+def mse_loss_per_sample_ws_floats(Bn, HW):
+    n = _l.query("mse_loss_per_sample_ws_floats", Bn, HW)
+    if n < 0:
+        raise RuntimeError(f"mse_loss_per_sample: unsupported shape Bn={Bn} HW={HW}")
+    return n
+
+
+def mse_loss_per_sample(pred, target, out, ws, Bn, Lc, HW):
+    """out[b] = mean over (c, p) of (pred - target)^2 of sample b (forward only; layouts of mse_loss_grad)"""
+    assert out.dtype == torch.float32 and out.numel() >= Bn and ws.dtype == torch.float32
+    assert ws.numel() >= mse_loss_per_sample_ws_floats(Bn, HW), "mse_loss_per_sample: workspace too small"
+    _l.call("mse_loss_per_sample", _p(pred), _ld(pred), _p(target), _p(out), _p(ws), Bn, Lc, HW, stream())
+
+
 OPT_CHECK, OPT_APPLY, OPT_FINISH, OPT_ALL = 1, 2, 4, 7
 
 
