@@ -17,12 +17,14 @@ read from a device table so that the step still replays as one graph (vneti_cfg_
 """
 from __future__ import annotations
 
+from functools import partial
 from typing import Dict, List, Optional, Sequence
 
 import torch
 
 from .. import lib, ops
 from .. import sd_config as sc
+from .graphs import capture_graphs
 from .step import alphas_cumprod
 from .text import MapperState, TextEngine, flatten_mapper_state
 from .unet import UNetEngine
@@ -41,19 +43,24 @@ def inference_timesteps(kind: str, num_steps: int, num_train: int = 1000) -> Lis
     raise ValueError(f"unknown sampler {kind!r} (dpm++2m | ddim)")
 
 
-def step_coefficients(kind: str, ac: torch.Tensor, timesteps: Sequence[int], i: int):
-    """(cx, c0, c1, alpha_t, sigma_t) of step i, all in f64 on the host.  DPM-Solver++ 2M with diffusers'
-    defaults (solver_order 2, midpoint, lower_order_final for < 15 steps); DDIM eta=0, set_alpha_to_one=False."""
+def coefficient_row(kind: str, ac: torch.Tensor, timesteps: Sequence[int], i: int, eta: float = 0.0):
+    """(alpha_t, sigma_t, cx, c0, c1, cn) of step i — one row of the 6-column device table, the eta = 0 table holds its
+    first five — all in f64 on the host.  DPM-Solver++ 2M with diffusers' defaults (solver_order 2, midpoint,
+    lower_order_final for < 15 steps).  DDIM is DDIMScheduler.step with its `eta`, set_alpha_to_one=False:
+        std = eta sqrt((1 - a_prev)/(1 - a_t) (1 - a_t/a_prev))
+        x_prev = sqrt(a_prev) x0 + sqrt(1 - a_prev - std^2) eps + std noise,   eps = (x - sqrt(a_t) x0)/sqrt(1 - a_t)
+    i.e. x <- cx x + c0 x0 + cn noise with r = sqrt((1 - a_prev - std^2)/(1 - a_t)): cx = r, c0 = sqrt(a_prev) - r sqrt(a_t),
+    cn = std (eta = 0: std^2 = 0 leaves every operation of the deterministic step as it is)."""
     ac = ac.double().cpu()
     t = timesteps[i]
-    al, sg = ac.sqrt(), (1 - ac).sqrt()
     if kind == "ddim":
-        ratio = ac.numel() // len(timesteps)
-        tp = t - ratio
+        tp = t - ac.numel() // len(timesteps)
         a_t = ac[t]
         a_p = ac[tp] if tp >= 0 else ac[0]
-        r = ((1 - a_p) / (1 - a_t)).sqrt()
-        return float(r), float(a_p.sqrt() - r * a_t.sqrt()), 0.0, float(al[t]), float(sg[t])
+        std = float(eta) * ((1 - a_p) / (1 - a_t) * (1 - a_t / a_p)).sqrt()
+        r = ((1 - a_p - std ** 2) / (1 - a_t)).sqrt()
+        return (float(a_t.sqrt()), float((1 - a_t).sqrt()), float(r), float(a_p.sqrt() - r * a_t.sqrt()), 0.0, float(std))
+    al, sg = ac.sqrt(), (1 - ac).sqrt()
     lam = al.log() - sg.log()
     n = len(timesteps)
     tp = 0 if i == n - 1 else timesteps[i + 1]
@@ -61,28 +68,22 @@ def step_coefficients(kind: str, ac: torch.Tensor, timesteps: Sequence[int], i: 
     cx = sg[tp] / sg[t]
     base = -al[tp] * (torch.exp(-h) - 1.0)
     if i == 0 or (i == n - 1 and n < 15):
-        return float(cx), float(base), 0.0, float(al[t]), float(sg[t])
+        return float(al[t]), float(sg[t]), float(cx), float(base), 0.0, 0.0
     r0 = (lam[t] - lam[timesteps[i - 1]]) / h
-    return float(cx), float(base * (1 + 0.5 / r0)), float(-0.5 * base / r0), float(al[t]), float(sg[t])
+    return float(al[t]), float(sg[t]), float(cx), float(base * (1 + 0.5 / r0)), float(-0.5 * base / r0), 0.0
+
+
+def step_coefficients(kind: str, ac: torch.Tensor, timesteps: Sequence[int], i: int):
+    """(cx, c0, c1, alpha_t, sigma_t) of step i at eta = 0 (coefficient_row in the samplers' own order)"""
+    a_t, s_t, cx, c0, c1, _ = coefficient_row(kind, ac, timesteps, i)
+    return cx, c0, c1, a_t, s_t
 
 
 def ddim_eta_coefficients(ac: torch.Tensor, timesteps: Sequence[int], i: int, eta: float):
-    """(alpha_t, sigma_t, cx, c0, c1, cn) of DDIM step i with the scheduler's `eta` (one row of the 6-column device table),
-    f64 on the host.  DDIMScheduler.step, set_alpha_to_one=False:
-        std = eta sqrt((1 - a_prev)/(1 - a_t) (1 - a_t/a_prev))
-        x_prev = sqrt(a_prev) x0 + sqrt(1 - a_prev - std^2) eps + std noise,   eps = (x - sqrt(a_t) x0)/sqrt(1 - a_t)
-    i.e. x <- cx x + c0 x0 + cn noise with r = sqrt((1 - a_prev - std^2)/(1 - a_t)): cx = r, c0 = sqrt(a_prev) - r sqrt(a_t),
-    cn = std.  eta = 0 gives step_coefficients("ddim", ...) exactly (std^2 = 0 leaves every operation as it is there)."""
+    """(alpha_t, sigma_t, cx, c0, c1, cn) of DDIM step i with the scheduler's `eta`: coefficient_row("ddim", ...)"""
     if eta < 0:
         raise ValueError(f"eta = {eta}: DDIM's eta lies in [0, 1] (0: deterministic, 1: DDPM-like variance)")
-    ac = ac.double().cpu()
-    t = timesteps[i]
-    tp = t - ac.numel() // len(timesteps)
-    a_t = ac[t]
-    a_p = ac[tp] if tp >= 0 else ac[0]
-    std = float(eta) * ((1 - a_p) / (1 - a_t) * (1 - a_t / a_p)).sqrt()
-    r = ((1 - a_p - std ** 2) / (1 - a_t)).sqrt()
-    return (float(a_t.sqrt()), float((1 - a_t).sqrt()), float(r), float(a_p.sqrt() - r * a_t.sqrt()), 0.0, float(std))
+    return coefficient_row("ddim", ac, timesteps, i, eta)
 
 
 def check_eta(kind: str, eta: float) -> bool:
@@ -193,14 +194,12 @@ class InferenceEngine:
         # device tables a captured sampler step reads (row = step_idx): {alpha_t, sigma_t, cx, c0, c1}, timestep
         self.coef_table = torch.zeros((cfg.ddpm.num_train_timesteps, 5), dtype=torch.float32, device=device)
         self.ts_table = torch.zeros((cfg.ddpm.num_train_timesteps,), dtype=torch.int64, device=device)
-        self._graph = None
-        self._graph_key = None
         # stochastic DDIM (eta > 0): a 6-column table (+ cn) and the per-step variance noise [T][B][Lc][h][w], allocated
-        # at the first such call; the captured step that reads them is cached beside the eta = 0 one
+        # at the first such call
         self.coef_table6 = torch.zeros((cfg.ddpm.num_train_timesteps, 6), dtype=torch.float32, device=device)
         self.noise_table = None
-        self._graph_noise = None
-        self._graph_noise_key = None
+        # captured sampler steps by (guidance_scale, vpred, noisy): one with and one without the noise term at a time
+        self._graphs = {}
 
     # ------------------------------------------------------------------ conditioning
     def set_negative_prompt(self, input_ids: torch.Tensor):
@@ -262,49 +261,59 @@ class InferenceEngine:
         eta > 0 (DDIM only): DDIMScheduler.step's variance term, fed from step_noise, f32 [T][B][4][h][w] N(0,1) (one draw
         per sampler step; None: drawn here from torch's global generator, as the scheduler does without a generator).
         Returns the images f32 [B, H, W, 3] in [0,1] (the array `numpy_to_pil` receives) or the final latents."""
+        ts = self._timesteps(kind, num_inference_steps, guidance_scale)
+        return self._sample(latents, ts, guidance_scale, kind, decode, eta, step_noise, self._own_conditioning, use_graph)
+
+    def _timesteps(self, kind, num_inference_steps, guidance_scale):
         if guidance_scale <= 1.0:
             raise ValueError("sd_pipeline_call only defines the classifier-free-guidance branch (guidance_scale > 1)")
+        return inference_timesteps(kind, num_inference_steps, self.cfg.ddpm.num_train_timesteps)
+
+    def _own_conditioning(self, i, t):
+        """eager step i at timestep t: the engine's text pass writes the conditional half of the UNet's contexts"""
         B, L = self.B, self.L
-        ts = inference_timesteps(kind, num_inference_steps, self.cfg.ddpm.num_train_timesteps)
-        if check_eta(kind, eta):
-            return self._generate_eta(latents, ts, guidance_scale, decode, use_graph, eta, step_noise)
-        self.x.copy_(latents)
-        self.m_prev.zero_()
-        self.unet.x_in[:B].copy_(self.x)
-        self.unet.x_in[B:].copy_(self.x)
+        self.t_text.fill_(t)
+        self.unet.timesteps.fill_(t)
+        self.text.forward()
+        self.unet.ctx_k[:, B * L:].copy_(self.ctx_k)
+        self.unet.ctx_v[:, B * L:].copy_(self.ctx_v)
+
+    def _sample(self, latents, ts, guidance_scale, kind, decode, eta, step_noise, conditioning, use_graph):
+        """the sampler loop behind generate() and generate_from_contexts().  conditioning(i, t) sets the timestep and the
+        conditional contexts of eager step i; use_graph replays one captured step instead (which runs the engine's own
+        text pass: timesteps and step scalars come from device tables).  eta > 0 (`noisy`) swaps the sampler launch for
+        its noise-table sibling and nothing else."""
+        noisy = check_eta(kind, eta)
         vpred = self.cfg.ddpm.prediction_type == "v_prediction"
+        self._seed(latents)
+        if noisy:
+            self._load_step_noise(step_noise, len(ts))
+        rows = [coefficient_row(kind, self.ac, ts, i, eta) for i in range(len(ts))]
         if use_graph:
-            # one captured sampler step, replayed T times: timesteps and step scalars come from device tables
-            rows = [step_coefficients(kind, self.ac, ts, i) for i in range(len(ts))]
-            self.coef_table[: len(ts)].copy_(torch.tensor([[a, s_, cx, c0, c1] for (cx, c0, c1, a, s_) in rows],
-                                                          dtype=torch.float32))
+            table = self.coef_table6 if noisy else self.coef_table
+            table[: len(ts)].copy_(torch.tensor([r[: table.shape[1]] for r in rows], dtype=torch.float32))
             self.ts_table[: len(ts)].copy_(torch.tensor(ts, dtype=torch.int64))
             self.step_idx.zero_()
-            key = (guidance_scale, vpred)
-            if self._graph is None or self._graph_key != key:
-                self._capture(guidance_scale, vpred)
-                self._graph_key = key
+            key = (guidance_scale, vpred, noisy)  # eta itself lives in the table: one graph serves every eta > 0
+            if key not in self._graphs:
+                self._graphs = {k: g for k, g in self._graphs.items() if k[2] != noisy}
+                self._graphs[key] = self._capture(guidance_scale, vpred, noisy)
                 self.step_idx.zero_()
-                self.x.copy_(latents)
-                self.m_prev.zero_()
-                self.unet.x_in[:B].copy_(self.x)
-                self.unet.x_in[B:].copy_(self.x)
+                self._seed(latents)
             for _ in ts:
-                self._graph.replay()
+                self._graphs[key].replay()
         else:
+            B, n = self.B, self.h * self.w
             for i, t in enumerate(ts):
-                self.t_text.fill_(t)
-                self.unet.timesteps.fill_(t)
-                self.text.forward()
-                self.unet.ctx_k[:, B * L:].copy_(self.ctx_k)
-                self.unet.ctx_v[:, B * L:].copy_(self.ctx_v)
+                conditioning(i, t)
                 self.unet.forward()
-                cx, c0, c1, a_t, s_t = step_coefficients(kind, self.ac, ts, i)
-                ops.cfg_sampler_step(self.unet.pred, self.x, self.m_prev, self.unet.x_in, B, self.Lc,
-                                     self.h * self.w, guidance_scale, a_t, s_t, cx, c0, c1, vpred)
-        if not decode:
-            return self.x
-        return self.decode()
+                if noisy:
+                    ops.cfg_sampler_step_noise(self.unet.pred, self.x, self.m_prev, self.unet.x_in, self.noise_table[i], B,
+                                               self.Lc, n, guidance_scale, *rows[i], vpred)
+                else:
+                    ops.cfg_sampler_step(self.unet.pred, self.x, self.m_prev, self.unet.x_in, B, self.Lc, n,
+                                         guidance_scale, *rows[i][:5], vpred)
+        return self.decode() if decode else self.x
 
     def decode(self) -> torch.Tensor:
         """decode self.x into self.image, `decode_batch` samples per decoder pass"""
@@ -357,36 +366,19 @@ class InferenceEngine:
         (sd_pipeline_call.py:86: `prompt_embeds[i] if type(prompt_embeds) == list else prompt_embeds`): a list of T
         per-step XTI dicts (PromptManager.embed_prompt's return value, prompt_manager.py:79-99), one dict, or one tensor.
         The engine's own text pass is skipped; the negative prompt must have been set (set_negative_prompt)."""
-        if guidance_scale <= 1.0:
-            raise ValueError("sd_pipeline_call only defines the classifier-free-guidance branch (guidance_scale > 1)")
-        B = self.B
-        ts = inference_timesteps(kind, num_inference_steps, self.cfg.ddpm.num_train_timesteps)
-        if type(prompt_embeds) == list and len(prompt_embeds) < len(ts):
+        ts = self._timesteps(kind, num_inference_steps, guidance_scale)
+        per_step = type(prompt_embeds) == list
+        if per_step and len(prompt_embeds) < len(ts):
             raise ValueError(f"{len(prompt_embeds)} per-step prompt embeddings for {len(ts)} sampler steps")
-        self.x.copy_(latents)
-        self.m_prev.zero_()
-        self.unet.x_in[:B].copy_(self.x)
-        self.unet.x_in[B:].copy_(self.x)
-        vpred = self.cfg.ddpm.prediction_type == "v_prediction"
-        noisy = check_eta(kind, eta)
-        if noisy:
-            self._load_step_noise(step_noise, len(ts))
-        if type(prompt_embeds) != list:
+        if not per_step:
             self.load_contexts(prompt_embeds)
-        for i, t in enumerate(ts):
-            if type(prompt_embeds) == list:
+
+        def conditioning(i, t):
+            if per_step:
                 self.load_contexts(prompt_embeds[i])
             self.unet.timesteps.fill_(t)
-            self.unet.forward()
-            if noisy:
-                self._eager_noise_step(ts, i, guidance_scale, vpred, eta)
-                continue
-            cx, c0, c1, a_t, s_t = step_coefficients(kind, self.ac, ts, i)
-            ops.cfg_sampler_step(self.unet.pred, self.x, self.m_prev, self.unet.x_in, B, self.Lc, self.h * self.w,
-                                 guidance_scale, a_t, s_t, cx, c0, c1, vpred)
-        if not decode:
-            return self.x
-        return self.decode()
+
+        return self._sample(latents, ts, guidance_scale, kind, decode, eta, step_noise, conditioning, use_graph=False)
 
     # ------------------------------------------------------------------ stochastic DDIM (eta > 0)
     def _load_step_noise(self, step_noise: Optional[torch.Tensor], T: int) -> None:
@@ -399,13 +391,8 @@ class InferenceEngine:
             raise ValueError(f"step_noise of shape {tuple(step_noise.shape)} {step_noise.dtype}: expected f32 {shape}")
         if self.noise_table is None or self.noise_table.shape[0] < T:
             self.noise_table = torch.empty(shape, dtype=torch.float32, device=self.dev)
-            self._graph_noise = None
+            self._graphs = {k: g for k, g in self._graphs.items() if not k[2]}
         self.noise_table[:T].copy_(step_noise)
-
-    def _eager_noise_step(self, ts, i, guidance_scale, vpred, eta):
-        a_t, s_t, cx, c0, c1, cn = ddim_eta_coefficients(self.ac, ts, i, eta)
-        ops.cfg_sampler_step_noise(self.unet.pred, self.x, self.m_prev, self.unet.x_in, self.noise_table[i], self.B,
-                                   self.Lc, self.h * self.w, guidance_scale, a_t, s_t, cx, c0, c1, cn, vpred)
 
     def _seed(self, latents):
         B = self.B
@@ -413,38 +400,6 @@ class InferenceEngine:
         self.m_prev.zero_()
         self.unet.x_in[:B].copy_(self.x)
         self.unet.x_in[B:].copy_(self.x)
-
-    def _generate_eta(self, latents, ts, guidance_scale, decode, use_graph, eta, step_noise):
-        """generate() for DDIM with eta > 0: the same loop with vneti_cfg_sampler_step_noise(_table) as its last launch"""
-        B, L = self.B, self.L
-        self._load_step_noise(step_noise, len(ts))
-        self._seed(latents)
-        vpred = self.cfg.ddpm.prediction_type == "v_prediction"
-        if use_graph:
-            rows = [ddim_eta_coefficients(self.ac, ts, i, eta) for i in range(len(ts))]
-            self.coef_table6[: len(ts)].copy_(torch.tensor(rows, dtype=torch.float32))
-            self.ts_table[: len(ts)].copy_(torch.tensor(ts, dtype=torch.int64))
-            self.step_idx.zero_()
-            key = (guidance_scale, vpred, True)  # eta itself lives in the table: one graph serves every eta > 0
-            if self._graph_noise is None or self._graph_noise_key != key:
-                self._graph_noise = self._capture(guidance_scale, vpred, noise=True)
-                self._graph_noise_key = key
-                self.step_idx.zero_()
-                self._seed(latents)
-            for _ in ts:
-                self._graph_noise.replay()
-        else:
-            for i, t in enumerate(ts):
-                self.t_text.fill_(t)
-                self.unet.timesteps.fill_(t)
-                self.text.forward()
-                self.unet.ctx_k[:, B * L:].copy_(self.ctx_k)
-                self.unet.ctx_v[:, B * L:].copy_(self.ctx_v)
-                self.unet.forward()
-                self._eager_noise_step(ts, i, guidance_scale, vpred, eta)
-        if not decode:
-            return self.x
-        return self.decode()
 
     def _one_step(self, guidance_scale, vpred, noise=False):
         B, L = self.B, self.L
@@ -464,21 +419,9 @@ class InferenceEngine:
         ops.counter_advance(self.step_idx)
 
     def _capture(self, guidance_scale, vpred, noise=False):
-        """capture one sampler step (the warm-up run below is a real step: the caller re-seeds x afterwards).  The eta = 0
-        step becomes self._graph; the noise-table step is returned to its caller."""
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self._one_step(guidance_scale, vpred, noise)
-            torch.cuda.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            if not noise:
-                self._graph = graph
-            with torch.cuda.graph(graph, stream=s):
-                self._one_step(guidance_scale, vpred, noise)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        return graph
+        """one sampler step as a graph (its warm-up run is a real step: the caller re-seeds x afterwards)"""
+        step = partial(self._one_step, guidance_scale, vpred, noise)
+        return capture_graphs([step], warmup=step)[0]
 
     def memory_bytes(self) -> int:
         noise = 0 if self.noise_table is None else self.noise_table.numel() * 4

@@ -56,8 +56,6 @@ class Schedule:
         # f32 scratch for split-K GEMM / q-split attention partials: one per schedule, so two schedules
         # may run concurrently on different streams (bind_workspace() pins it into every launch)
         self.ws = self._buf((16 * 2 ** 20,), torch.float32)
-        self.ws_side = None
-        self._side_stream = None
         self._gn_fusable: List[dict] = []
         self.gn_sums = None
         if ops._default_ws is None or ops._default_ws.device != torch.device(device, torch.cuda.current_device()):
@@ -71,8 +69,8 @@ class Schedule:
         return t
 
     def _tmp(self, name, rows, cols, dtype=None):
-        dtype = dtype or lib.act_dtype()
         """reusable scratch for backward temporaries (single stream => sequential lifetimes)."""
+        dtype = dtype or lib.act_dtype()
         key = f"{name}:{dtype}"
         n = rows * cols
         cur = self._scratch.get(key)
@@ -152,28 +150,24 @@ class Schedule:
         ~0.5 s per engine; results are cached per problem signature across engines."""
         if not torch.cuda.is_available():
             return
+        import json
         import os
-        cold = None if os.environ.get("VNETI_AUTOTUNE_HOT") else torch.empty(160 * 2 ** 20, dtype=torch.float32, device=self.dev)
+        from .. import parallel
         if os.environ.get("VNETI_AUTOTUNE_CANDS"):
             candidates = tuple(int(x) for x in os.environ["VNETI_AUTOTUNE_CANDS"].split(","))
-        cold_reps = int(os.environ.get("VNETI_AUTOTUNE_REPS", "9"))
-        warm_a = bool(int(os.environ.get("VNETI_AUTOTUNE_WARM_A", "1")))
+        how = _timing_switches(self.dev, reps)
         cache = Schedule._tile_cache
         # optional on-disk cache of the picks (profiling runs reuse a previous run's picks so that the rocprofv3
         # per-kernel averages are those of the step, not of the autotuner's probes)
         cache_path = os.environ.get("VNETI_AUTOTUNE_CACHE")
         if cache_path and os.path.exists(cache_path) and not cache:
-            import ast
-            import json
-            for k, v in json.load(open(cache_path)).items():
-                cache[ast.literal_eval(k)] = tuple(v)  # keys: repr() of tuples of ints / None / bools written below
+            cache.update(picks_from_json(json.load(open(cache_path))))
         n_before = len(cache)
         # data parallel: rank 0 measures, every rank replays ITS picks (ranks that tuned on their own pinned different
         # tiles / split-K factors: the weak-scaling value was then the slowest rank's private schedule).  The other ranks
         # wait here for rank 0's cache and find every problem of the (identical) schedule in it.  This is a COLLECTIVE, so
         # it happens only inside `parallel.shared_picks()` — which TrainStepEngine.__init__, run by every rank, opens —
         # and never for an engine that one rank builds on its own (rank 0's validation / inference engines).
-        from .. import parallel
         share = parallel.sharing_picks() and parallel._dist() is not None
         rank0 = (not share) or parallel._dist().get_rank() == 0
         if share and not rank0:
@@ -183,92 +177,51 @@ class Schedule:
                 if getattr(f, "func", None) is not ops.gemm or f.keywords.get("tile_hint"):
                     continue
                 key = self._gemm_key(f)
-                conv = f.keywords.get("conv")
-                # the 8-phase tiles (16 / 17) take either K order of an implicit conv at the same cost (their gather offsets
-                # are linear in the tap); chunk-major — the nine taps of a 64-channel chunk in consecutive K-tiles — keeps the
-                # re-reads of the input rows in L2 and wins on the wide layers (256 channels at 256^2: 326 -> 293 us cold)
-                try_cm = bool(conv) and not conv.get("ups") and not conv.get("korder") and \
-                    not (conv["mode"] == 2 and conv["stride"] == 2) and conv["Ci"] % 64 == 0 and conv["Ci"] >= 128
                 B_cm = None
                 if key not in cache:
-                    best, best_t = (0, 0, 0), float("inf")
-                    M_, N_, K_ = key[:3]
-                    # tile 18 = the halo-patch form of 17 (a block owns 16 x 16 pixels, the input patch stays in LDS for all
-                    # nine taps): stride-1 pad-1 3x3 convolutions (forward or transposed gather) on a 16-pixel grid, chunk-major K
-                    # only; split-K in whole channel chunks
-                    halo_ok = try_cm and conv["mode"] in (1, 2) and conv["stride"] == 1 and conv["pad_t"] == 1 and conv["pad_l"] == 1 \
-                        and conv["Ho"] % 16 == 0 and conv["Wo"] % 16 == 0 and conv["Hi"] == conv["Ho"] and conv["Wi"] == conv["Wo"]
-                    variants = [(h, 0) for h in candidates if h != 18] + \
-                        ([(h, 1) for h in candidates if h in (16, 17) or (h == 18 and halo_ok)] if try_cm else [])
-                    if try_cm:
-                        B_cm = packing._chunk_major(f.args[1], f.args[1].shape[0], conv["Ci"])
-                    for h, ko in variants:
-                        bm, bn = self._TILE_DIMS[h % 100]
-                        tiles = -(-M_ // bm) * -(-N_ // bn) * key[3]
-                        # 0 = library heuristic, 1 = no split, explicit factors where the grid leaves CUs idle and K is deep
-                        sks = (0, 1) + (tuple(x for x in (2, 3, 4, 6, 8, 12)
-                                              if x * 8 <= K_ // 64 and tiles * x <= 1024 and x * key[3] * M_ * N_ <= 16 * 2 ** 20)
-                                        if tiles < 256 else ())
-                        if f.keywords.get("geglu"):
-                            sks = (1,)  # the GEGLU epilogues do not exist in the split-K reduce kernel
-                        for sk in sks:
-                            kw = dict(f.keywords)
-                            kw["tile_hint"], kw["split_k"] = h, sk
-                            args = f.args
-                            if ko:
-                                kw["conv"] = dict(conv, korder=1)
-                                args = (f.args[0], B_cm) + tuple(f.args[2:])
-                            ops.gemm(*args, **kw)
-                            ops.gemm(*args, **kw)
-                            if cold is None:
-                                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                                s.record()
-                                for _ in range(reps):
-                                    ops.gemm(*args, **kw)
-                                e.record()
-                                e.synchronize()
-                                t = s.elapsed_time(e)
-                            else:
-                                # cold timing: inside the step a GEMM's weights (and everything older) were evicted by
-                                # its predecessors — a fill of a buffer larger than L2 + MALL between the timed launches
-                                # restores that — while its activation operand was written by the launch just before it:
-                                # a no-op in-place add re-touches it after the fill (picks move by +0.4 % on the step)
-                                ts = []
-                                for _ in range(cold_reps):
-                                    cold.fill_(0)
-                                    if warm_a:  # the activation operand as its producer just left it (L2 / MALL), weights cold
-                                        args[0].add_(0)  # (replaying the 2-4 preceding launches instead measured no better)
-                                    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                                    s.record()
-                                    ops.gemm(*args, **kw)
-                                    e.record()
-                                    e.synchronize()
-                                    ts.append(s.elapsed_time(e))
-                                t = sorted(ts)[len(ts) // 2]  # median: one slow outlier must not veto a candidate
-                            if t < best_t:
-                                best, best_t = (h, sk, ko), t
-                    cache[key] = best
-                pick = tuple(cache[key]) + (0,) * (3 - len(cache[key]))
-                kw = dict(f.keywords)
-                kw["tile_hint"], kw["split_k"] = pick[0], pick[1]
-                if pick[2] and try_cm:  # this launch runs chunk-major: its own re-ordered copy of the packed weight
-                    if B_cm is None:
-                        B_cm = packing._chunk_major(f.args[1], f.args[1].shape[0], conv["Ci"])
-                    kw["conv"] = dict(conv, korder=1)
-                    self.bytes += B_cm.numel() * B_cm.element_size()
-                    f_cm = partial(ops.gemm, f.args[0], B_cm, *f.args[2:], **f.keywords)
-                    if getattr(f, "side", False):
-                        f_cm.side = True
-                    f = f_cm
-                lst[idx] = self._rebound(f, ops.gemm, kw)
+                    cache[key], B_cm = self._measure(f, key, candidates, how)
+                lst[idx] = self._pin(f, cache[key], B_cm)
         if share and rank0:
             parallel.share_from_rank0(dict(cache))
         if cache_path and len(cache) != n_before and parallel.world_info()[0] == 0:
-            import json  # rank 0 only, and atomically: a concurrent or torn write would poison the next run's load
+            # rank 0 only, and atomically: a concurrent or torn write would poison the next run's load
             tmp = f"{cache_path}.{os.getpid()}.tmp"
             with open(tmp, "w") as fh:
-                json.dump({repr(k): list(v) for k, v in cache.items()}, fh)
+                json.dump(picks_to_json(cache), fh)
             os.replace(tmp, cache_path)
+
+    def _measure(self, f, key, candidates, how):
+        """time every variant of one GEMM launch (gemm_variants); returns the fastest (tile, split_k, korder) — the first
+        of equals — and the chunk-major copy of the packed weight if one was made for the probes"""
+        conv = f.keywords.get("conv")
+        B_cm = packing._chunk_major(f.args[1], f.args[1].shape[0], conv["Ci"]) if _chunk_major_ok(conv) else None
+        best, best_t = (0, 0, 0), float("inf")
+        for h, sk, ko in gemm_variants(key, conv, f.keywords.get("geglu"), candidates):
+            kw = dict(f.keywords)
+            kw["tile_hint"], kw["split_k"] = h, sk
+            args = f.args
+            if ko:
+                kw["conv"] = dict(conv, korder=1)
+                args = (f.args[0], B_cm) + tuple(f.args[2:])
+            t = _time_call(partial(ops.gemm, *args, **kw), args[0], *how)
+            if t < best_t:
+                best, best_t = (h, sk, ko), t
+        return best, B_cm
+
+    def _pin(self, f, pick, B_cm=None):
+        """the launch re-bound to its pick; a chunk-major pick runs on its own re-ordered copy of the packed weight"""
+        pick = tuple(pick) + (0,) * (3 - len(pick))
+        conv = f.keywords.get("conv")
+        kw = dict(f.keywords)
+        kw["tile_hint"], kw["split_k"] = pick[0], pick[1]
+        args = f.args
+        if pick[2] and _chunk_major_ok(conv):
+            if B_cm is None:
+                B_cm = packing._chunk_major(f.args[1], f.args[1].shape[0], conv["Ci"])
+            kw["conv"] = dict(conv, korder=1)
+            self.bytes += B_cm.numel() * B_cm.element_size()
+            args = (f.args[0], B_cm) + tuple(f.args[2:])
+        return partial(ops.gemm, *args, **kw)
 
     def bind_workspace(self):
         """pin this schedule's own split-K / q-split scratch into every launch that may use one."""
@@ -276,25 +229,11 @@ class Schedule:
             for idx, f in enumerate(lst):
                 fn = getattr(f, "func", None)
                 if fn is ops.gemm or fn is ops.attn_bwd_dkv:
-                    kw = dict(f.keywords)
-                    # launches that run on the side stream get their own scratch: they may overlap main-stream GEMMs
-                    kw["workspace"] = self.ws_side if getattr(f, "side", False) else self.ws
-                    lst[idx] = self._rebound(f, fn, kw)
+                    lst[idx] = self._rebound(f, fn, dict(f.keywords, workspace=self.ws))
 
     @staticmethod
     def _rebound(f, fn, kw):
-        p = partial(fn, *f.args, **kw)
-        if getattr(f, "side", False):
-            p.side = True
-        return p
-
-    def _side(self, launch):
-        """mark a launch as independent of the main chain until the end of the list: it is forked onto a second
-        stream (in a captured graph: a parallel branch) and joined when the list finishes."""
-        launch.side = True
-        if self.ws_side is None:
-            self.ws_side = self._buf((4 * 2 ** 20,), torch.float32)
-        return launch
+        return partial(fn, *f.args, **kw)
 
     # ------------------------------------------------------------------ GroupNorm statistics in the producer
     GN_SLOTS = 8  # (16 and 32 measured: no gain — the slot atomics are not what the statistics launches wait for)
@@ -524,45 +463,111 @@ class Schedule:
         self.forward_pre()
         self.forward_main()
 
-    def _run(self, lst):
-        side = None
-        main = None
-        for f in lst:
-            if getattr(f, "side", False):
-                if side is None:
-                    if self._side_stream is None:
-                        self._side_stream = torch.cuda.Stream()
-                    side, main = self._side_stream, torch.cuda.current_stream()
-                side.wait_stream(main)  # fork point: everything issued so far
-                with torch.cuda.stream(side):
-                    f()
-            else:
-                f()
-        if side is not None:
-            main.wait_stream(side)  # join
-
     def backward(self):
-        self._run(self.bwd)
+        for f in self.bwd:
+            f()
+
+
+# ---------------------------------------------------------------------- what the autotuner times, and how
+def _chunk_major_ok(conv) -> bool:
+    """the 8-phase tiles (16 / 17) take either K order of an implicit conv at the same cost (their gather offsets are
+    linear in the tap); chunk-major — the nine taps of a 64-channel chunk in consecutive K-tiles — keeps the re-reads of
+    the input rows in L2 and wins on the wide layers (256 channels at 256^2: 326 -> 293 us cold)"""
+    return bool(conv) and not conv.get("ups") and not conv.get("korder") and \
+        not (conv["mode"] == 2 and conv["stride"] == 2) and conv["Ci"] % 64 == 0 and conv["Ci"] >= 128
+
+
+def gemm_variants(key, conv, geglu, candidates) -> List[tuple]:
+    """the (tile, split_k, korder) variants the autotuner times for one problem, in timing order (the first of equally
+    fast ones wins).  key: Schedule._gemm_key's (M, N, K, batch, ...); conv: the launch's conv dict or None.  Pure."""
+    M, N, K, batch = key[:4]
+    try_cm = _chunk_major_ok(conv)
+    # tile 18 = the halo-patch form of 17 (a block owns 16 x 16 pixels, the input patch stays in LDS for all nine taps):
+    # stride-1 pad-1 3x3 convolutions (forward or transposed gather) on a 16-pixel grid, chunk-major K only; split-K in
+    # whole channel chunks
+    halo_ok = try_cm and conv["mode"] in (1, 2) and conv["stride"] == 1 and conv["pad_t"] == 1 and conv["pad_l"] == 1 \
+        and conv["Ho"] % 16 == 0 and conv["Wo"] % 16 == 0 and conv["Hi"] == conv["Ho"] and conv["Wi"] == conv["Wo"]
+    tiles_ko = [(h, 0) for h in candidates if h != 18] + \
+        ([(h, 1) for h in candidates if h in (16, 17) or (h == 18 and halo_ok)] if try_cm else [])
+    out = []
+    for h, ko in tiles_ko:
+        bm, bn = Schedule._TILE_DIMS[h]
+        tiles = -(-M // bm) * -(-N // bn) * batch
+        # 0 = library heuristic, 1 = no split, explicit factors where the grid leaves CUs idle and K is deep
+        sks = (0, 1) + (tuple(x for x in (2, 3, 4, 6, 8, 12)
+                              if x * 8 <= K // 64 and tiles * x <= 1024 and x * batch * M * N <= 16 * 2 ** 20)
+                        if tiles < 256 else ())
+        if geglu:
+            sks = (1,)  # the GEGLU epilogues do not exist in the split-K reduce kernel
+        out += [(h, sk, ko) for sk in sks]
+    return out
+
+
+def _timing_switches(dev, reps):
+    """(cold, reps, cold_reps, warm_a) of _time_call from the environment: VNETI_AUTOTUNE_HOT times cache-hot repeats
+    (cold = None) instead of filling a buffer larger than L2 + MALL before each of VNETI_AUTOTUNE_REPS launches;
+    VNETI_AUTOTUNE_WARM_A=0 leaves the activation operand cold too"""
+    import os
+    cold = None if os.environ.get("VNETI_AUTOTUNE_HOT") else torch.empty(160 * 2 ** 20, dtype=torch.float32, device=dev)
+    return (cold, reps, int(os.environ.get("VNETI_AUTOTUNE_REPS", "9")),
+            bool(int(os.environ.get("VNETI_AUTOTUNE_WARM_A", "1"))))
+
+
+def _time_call(call, act, cold, reps, cold_reps, warm_a):
+    """milliseconds of one bound launch after two untimed ones: `reps` cache-hot repeats together (cold is None), or the
+    median of `cold_reps` single cold launches"""
+    call()
+    call()
+
+    def timed(n):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(n):
+            call()
+        e.record()
+        e.synchronize()
+        return s.elapsed_time(e)
+
+    if cold is None:
+        return timed(reps)
+    # cold timing: inside the step a GEMM's weights (and everything older) were evicted by its predecessors — a fill of a
+    # buffer larger than L2 + MALL between the timed launches restores that — while its activation operand was written by
+    # the launch just before it: a no-op in-place add re-touches it after the fill (picks move by +0.4 % on the step)
+    ts = []
+    for _ in range(cold_reps):
+        cold.fill_(0)
+        if warm_a:  # the activation operand as its producer just left it (L2 / MALL), weights cold
+            act.add_(0)  # (replaying the 2-4 preceding launches instead measured no better)
+        ts.append(timed(1))
+    return sorted(ts)[len(ts) // 2]  # median: one slow outlier must not veto a candidate
 
 
 # ---------------------------------------------------------------------- the autotuner's picks as plain data
+def picks_to_json(cache: Dict) -> Dict:
+    """{repr(key): [tile, split_k, korder]}: the form of the VNETI_AUTOTUNE_CACHE file and of a trainer state's picks"""
+    return {repr(k): [int(x) for x in v] for k, v in cache.items()}
+
+
+def picks_from_json(data: Dict) -> Dict:
+    """the inverse: keys are repr() of tuples of ints / None / bools"""
+    import ast
+    return {ast.literal_eval(k): tuple(int(x) for x in v) for k, v in data.items()}
+
+
 def export_picks() -> Dict:
     """the picks pinned so far in this process, in the repr-keyed form of the VNETI_AUTOTUNE_CACHE JSON, stamped with the
     kernel tree they were timed on.  A trainer state carries them: two engines compute bit-identical steps only with the
     same tile / split-K / K-order per GEMM, and picks are TIMED, so a second process may pin others."""
     from ..roofline import kernel_tree_sha
-    return {"kernel_tree_sha": kernel_tree_sha(),
-            "picks": {repr(k): [int(x) for x in v] for k, v in Schedule._tile_cache.items()}}
+    return {"kernel_tree_sha": kernel_tree_sha(), "picks": picks_to_json(Schedule._tile_cache)}
 
 
 def preload_picks(data: Dict) -> bool:
     """pin exported picks before any engine is built (engines built afterwards find their problems in the cache and time
     nothing).  Picks timed on another kernel tree are refused — nothing is loaded, False is returned — and the caller's
     engines tune afresh."""
-    import ast
     from ..roofline import kernel_tree_sha
     if data.get("kernel_tree_sha") != kernel_tree_sha():
         return False
-    for k, v in data["picks"].items():
-        Schedule._tile_cache[ast.literal_eval(k)] = tuple(int(x) for x in v)
+    Schedule._tile_cache.update(picks_from_json(data["picks"]))
     return True

@@ -19,12 +19,14 @@ flat mapper-gradient bucket instead of wrapping the text encoder in DDP.
 """
 from __future__ import annotations
 
+from functools import partial
 from typing import Dict, List, Optional
 
 import torch
 
 from .. import ops
 from .. import sd_config as sc
+from .graphs import capture_graphs
 from .text import MapperState, TextEngine
 from .unet import UNetEngine
 from .vae import VAEEncoderEngine
@@ -185,6 +187,8 @@ class TrainStepEngine:
         self.side = torch.cuda.Stream() if overlap else None
         self.graph_a = self.graph_b = self.graph_acc = None
         self.exchange_in_graph = False
+        self._reduce_stage = None  # packed [scene segment | view mapper] gradients of a several-object exchange
+        self.last_reduce_bytes = 0
         self.micro = 0
         self._eval_batch = False  # the current batch was set for eval_losses(): not to be trained on
         self.n_loss = batch * Lc * self.h * self.w
@@ -299,13 +303,25 @@ class TrainStepEngine:
             ops.rng_fill_randint(self.timesteps, self.cfg.ddpm.num_train_timesteps, self.rng_state, 0)
             ops.rng_fill_normal(self.eps, self.rng_state, 1)
             ops.rng_fill_normal(self.noise, self.rng_state, 2)
-        # overlap=True forks: the 16 mapper+CLIP passes (many small launches) run beside the VAE encoder (few large ones) on
+        self._forward_half(cached, bool(self.n_cache), fork=self.overlap)
+        self.loss_sum.zero_()
+        ops.mse_loss_grad(self.unet.pred, self.target, self.unet.dpred, self.loss_sum, self.scaler, B, Lc, hw)
+        if self.need_backward:
+            self.unet.backward()
+            self.text.backward()
+
+    def _forward_half(self, cached: bool, write_cache: bool, fork: bool = False):
+        """VAE moments -> sample_add_noise -> text pass -> UNet forward, shared by the train step and the held-out
+        evaluation.  cached: the moments come out of the moment cache (no encoder launches); write_cache: the encoder's
+        moments are stored at the batch's image slots."""
+        B, Lc, hw = self.B, self.cfg.vae.latent_channels, self.h * self.w
+        # fork (overlap=True): the 16 mapper+CLIP passes (many small launches) run beside the VAE encoder (few large ones) on
         # a second stream; each schedule owns its split-K scratch, so they never alias.  OFF by default since round 6: both
         # sides fill the chip, and the two cross-stream edges of the captured graph cost more than the overlap returns
         # (same box, alternating processes: 39.96 / 39.98 / 40.05 steps/s without the fork, 39.08 / 39.75 / 39.79 with it;
         # profiles/r06_halo_persist_ab.txt) — the step is ONE linear chain of launches
-        main = torch.cuda.current_stream()
-        if self.overlap:
+        if fork:
+            main = torch.cuda.current_stream()
             self.side.wait_stream(main)
             with torch.cuda.stream(self.side):
                 self.text.forward()
@@ -314,22 +330,17 @@ class TrainStepEngine:
             torch.index_select(self.mcache, 0, self.img_idx, out=self.vae.moments.view(B, hw, 2 * Lc))
         else:
             self.vae.forward()
-            if self.n_cache:
+            if write_cache:
                 self.mcache.index_copy_(0, self.img_idx, self.vae.moments.view(B, hw, 2 * Lc))
         ops.sample_add_noise(self.vae.moments, self.eps, self.noise, self.timesteps, self.ac,
                              self.cfg.vae.scaling_factor, self.cfg.ddpm.prediction_type == "v_prediction", self.latents,
                              self.unet.x_in, self.target, B, Lc, hw)
-        if self.overlap:
+        if fork:
             main.wait_stream(self.side)  # join
         else:
             self.text.forward()
             self.unet.forward_pre()
         self.unet.forward_main()
-        self.loss_sum.zero_()
-        ops.mse_loss_grad(self.unet.pred, self.target, self.unet.dpred, self.loss_sum, self.scaler, B, Lc, hw)
-        if self.need_backward:
-            self.unet.backward()
-            self.text.backward()
 
     def optimizer_step(self):
         a = (self.hyper, self.scaler, self.opt_step, self.growth_interval)
@@ -359,13 +370,7 @@ class TrainStepEngine:
         mode = self.text.training
         self.text.training = False
         try:
-            self.vae.forward()
-            ops.sample_add_noise(self.vae.moments, self.eps, self.noise, self.timesteps, self.ac,
-                                 self.cfg.vae.scaling_factor, self.cfg.ddpm.prediction_type == "v_prediction", self.latents,
-                                 self.unet.x_in, self.target, B, Lc, hw)
-            self.text.forward()
-            self.unet.forward_pre()
-            self.unet.forward_main()
+            self._forward_half(cached=False, write_cache=False)
             ops.mse_loss_per_sample(self.unet.pred, self.target, self.eval_out, self.eval_ws, B, Lc, hw)
         finally:
             self.text.training = mode
@@ -387,17 +392,7 @@ class TrainStepEngine:
 
     def _capture_eval(self):
         """the warm-up launch is an evaluation itself: nothing to snapshot"""
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self.eval_forward()
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=s):
-                self.eval_forward()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        self.graph_eval = g
+        self.graph_eval = capture_graphs([self.eval_forward], warmup=self.eval_forward)[0]
 
     def all_reduce(self):
         """the one exchange step of data-parallel training: sum the mapper gradients over ranks
@@ -406,10 +401,9 @@ class TrainStepEngine:
         if self.world_size > 1:
             from ..parallel import all_reduce_plan_, reduce_plan
             plan = reduce_plan(self.n_obj, self.n_objects, self.active_object, self.grads.numel())
-            if len(plan) > 1 and getattr(self, "_reduce_stage", None) is None:  # scene segment + view mapper, packed
+            if len(plan) > 1 and self._reduce_stage is None:  # scene segment + view mapper, packed
                 self._reduce_stage = torch.empty(sum(b - a for a, b in plan), dtype=self.grads.dtype, device=self.grads.device)
-            self.last_reduce_bytes = all_reduce_plan_(self.grads, plan, getattr(self, "_reduce_stage", None),
-                                                      comm=self.exchange)
+            self.last_reduce_bytes = all_reduce_plan_(self.grads, plan, self._reduce_stage, comm=self.exchange)
 
     def _exchange_capturable(self) -> bool:
         """the all-reduce may sit INSIDE a graph: a stream-ordered library communicator, and a plan that does not depend on
@@ -504,43 +498,35 @@ class TrainStepEngine:
             self.micro = 0
 
     def _capture_graphs(self, exchange_in_graph: bool):
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
+        fused_opt = (self.world_size == 1 or exchange_in_graph) and self.grad_accum == 1
+        self.exchange_in_graph = exchange_in_graph
+
+        def micro_step(accumulate, cached):
+            self.forward_backward(accumulate=accumulate, cached=cached)
+            if fused_opt:  # (only without accumulation)
+                self.all_reduce()  # no-op at world 1; one captured collective node otherwise
+                self.optimizer_step()
+
+        def exchange_and_optimizer():
+            if exchange_in_graph:
+                self.all_reduce()
+            self.optimizer_step()
+
+        # capture order: a, acc, a_c, acc_c, b.  The _c graphs are the same steps with the moments read from the cache
+        # instead of the encoder
+        names = {(False, False): "graph_a", (True, False): "graph_acc", (False, True): "graph_a_c", (True, True): "graph_acc_c"}
+        plan = [(names[acc, cached], partial(micro_step, acc, cached))
+                for cached in ((False, True) if self.n_cache else (False,))
+                for acc in ((False, True) if self.grad_accum > 1 else (False,))]
+        if not fused_opt:
+            plan.append(("graph_b", exchange_and_optimizer))
+
+        def warmup():  # real steps on the capture stream (also primes RCCL): _capture() restores the state
             for _ in range(self.grad_accum):
-                self.step_eager()  # warm-up on the side stream (also primes RCCL)
-            torch.cuda.synchronize()
-            fused_opt = (self.world_size == 1 or exchange_in_graph) and self.grad_accum == 1
-            self.exchange_in_graph = exchange_in_graph
-            self.graph_a = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph_a, stream=s):
-                self.forward_backward(accumulate=False)
-                if fused_opt:
-                    self.all_reduce()  # no-op at world 1; one captured collective node otherwise
-                    self.optimizer_step()
-            if self.grad_accum > 1:
-                self.graph_acc = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph_acc, stream=s):
-                    self.forward_backward(accumulate=True)
-            if self.n_cache:  # the same steps with the moments read from the cache instead of the encoder
-                self.graph_a_c = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph_a_c, stream=s):
-                    self.forward_backward(accumulate=False, cached=True)
-                    if fused_opt:
-                        self.all_reduce()
-                        self.optimizer_step()
-                if self.grad_accum > 1:
-                    self.graph_acc_c = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(self.graph_acc_c, stream=s):
-                        self.forward_backward(accumulate=True, cached=True)
-            if not fused_opt:
-                self.graph_b = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph_b, stream=s):
-                    if exchange_in_graph:
-                        self.all_reduce()
-                    self.optimizer_step()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
+                self.step_eager()
+
+        for (name, _), graph in zip(plan, capture_graphs([body for _, body in plan], warmup)):
+            setattr(self, name, graph)
         if self.graph_eval is not None:  # captured before this (re-)capture: renew it with the others
             self.graph_eval = None
             self._capture_eval()
