@@ -1,5 +1,5 @@
 """Per-kernel parity of the bf16 build: every case of the kernel files (tests/test_kernels_gpu.py, tests/test_text_kernels_gpu.py,
-tests/test_optim_rng_gpu.py) against libvneti_hip_bf16.so.
+tests/test_optim_rng_gpu.py, tests/test_kernel_contracts_gpu.py) against libvneti_hip_bf16.so.
 
 A process computes in ONE 16-bit format (view_neti_amd/lib.py), so the bf16 run of the kernel file is a child pytest
 process with VNETI_PRECISION=bf16, one per GROUP of the file (so that a failure names its area and each child has a time
@@ -27,6 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KERNEL_FILE = os.path.join("tests", "test_kernels_gpu.py")
 TEXT_FILE = os.path.join("tests", "test_text_kernels_gpu.py")
 OPTIM_RNG_FILE = os.path.join("tests", "test_optim_rng_gpu.py")
+CONTRACTS_FILE = os.path.join("tests", "test_kernel_contracts_gpu.py")
 
 # group -> (kernel file, `-k` expression, time limit of the child in seconds).  The limits are several times the wall times
 # measured on an MI355X (the tables of the per-kernel parity runs), and never above 300 s.
@@ -41,9 +42,13 @@ GROUPS = {
     "optimizer": (OPTIM_RNG_FILE, "adamw", 120),
     "rng": (OPTIM_RNG_FILE, "test_rng or dropout", 150),
     "infer_helpers": (OPTIM_RNG_FILE, "conv1x1 or table_fill", 60),
+    "contracts_gemm": (CONTRACTS_FILE, "contract_gemm", 60),
+    "contracts_conv": (CONTRACTS_FILE, "contract_conv", 60),
+    "contracts_norms": (CONTRACTS_FILE, "contract_norm", 60),
+    "contracts_attention": (CONTRACTS_FILE, "contract_attn", 60),
 }
 # kernel file -> the least number of cases its collection must hold (a file that lost its tests cannot pass as "covered")
-KERNEL_FILES = {KERNEL_FILE: 500, TEXT_FILE: 120, OPTIM_RNG_FILE: 30}
+KERNEL_FILES = {KERNEL_FILE: 500, TEXT_FILE: 120, OPTIM_RNG_FILE: 30, CONTRACTS_FILE: 100}
 DEATH_CODES = (124, 134, 137, 139)  # time limit, abort, kill, segmentation fault (a negative code is a signal)
 
 _dead = None        # "group X died with rc N": set once, read by every later group
