@@ -391,6 +391,53 @@ int vneti_adamw_flat(float* p, const float* g, float* m, float* v, long long n, 
 int vneti_adamw_segments(float* p, const float* g, float* m, float* v, long long seg_len, int n_seg,
                          int* seg_step, const int* active, int n_active, const float* hyper,
                          float* scaler, int* step, int growth_interval, int phases, void* stream);
+/* Gradient norm on the device (extension: optim.max_grad_norm, log.train_metrics).
+ * vneti_grad_sumsq: the sum of squares of an f32 gradient bucket as f64 partials, one per chunk of a fixed partition that
+ * depends on `len` only (fixed-order reduction, no atomics: deterministic).  active == NULL (n_active 0): the flat range
+ * g[0, len).  Otherwise the n_active (1..8) segments of `len` floats named by the device int32 array `active`, the
+ * addressing of vneti_adamw_segments.  No alignment of g is assumed.  ws: vneti_grad_sumsq_ws_doubles(len, n_active)
+ * doubles, 8-byte aligned (negative: bad shape).  Squares are taken in f64: the sum is non-finite exactly when an element
+ * is (3.2e38 is a finite gradient). */
+long long vneti_grad_sumsq_ws_doubles(long long len, int n_active);
+int vneti_grad_sumsq(const float* g, long long len, const int* active, int n_active, void* ws, void* stream);
+/* One block: adds the n_object partials of ws_object, then the n_view partials of ws_view (either side may be absent: n 0),
+ * in index order in f64.  out (f32[VNETI_NORM_OUT_FLOATS]) = {norm_object, norm_view, norm_total, finite, clip_coef}:
+ * norms of the unscaled mean gradient, sqrt(sum) / (scaler[0] * hyper[5]), -1 for an absent side; finite 0/1;
+ * clip_coef = min(1, max_norm[0] / (norm_total + 1e-6)) (torch.nn.utils.clip_grad_norm_), exactly 1 when max_norm[0] <= 0
+ * (clipping off) or the sum is non-finite (the step is skipped).  max_norm: device f32[1].  ring (optional, with count /
+ * rows / row_floats as vneti_train_record): the same values, scaler[0] and hyper[0] (the lr) go into the row of the
+ * micro-step that closed the group, (count[0] - 1) % rows, and its VNETI_TELEMETRY_CLOSED flag is set. */
+#define VNETI_NORM_OUT_FLOATS 5
+int vneti_grad_norm_finish(const void* ws_object, long long n_object, const void* ws_view, long long n_view,
+                           const float* scaler, const float* hyper, const float* max_norm, float* out, float* ring,
+                           const int* count, int rows, int row_floats, void* stream);
+/* vneti_adamw_flat / vneti_adamw_segments with the unscaled gradient multiplied by clip_coef[0] (device f32, out + 4 of
+ * vneti_grad_norm_finish): g / (loss_scale * grad_div) * clip_coef[0].  Phases, the skip on found_inf, the per-segment
+ * step counts and the static-scale rule are those of the unclipped entries; a coefficient of exactly 1 changes no bit. */
+int vneti_adamw_flat_clipped(float* p, const float* g, float* m, float* v, long long n, const float* hyper,
+                             float* scaler, int* step, int growth_interval, int phases, const float* clip_coef,
+                             void* stream);
+int vneti_adamw_segments_clipped(float* p, const float* g, float* m, float* v, long long seg_len, int n_seg,
+                                 int* seg_step, const int* active, int n_active, const float* hyper, float* scaler,
+                                 int* step, int growth_interval, int phases, const float* clip_coef, void* stream);
+/* Per-step training record: a device ring of `rows` rows of row_floats = VNETI_TELEMETRY_HEADER + 2 * Bn floats, one row per
+ * micro-step, and a device int32 counter of the micro-steps recorded.  One launch writes row count[0] % rows — the
+ * sequence number (count mod 2^24), the micro index inside the accumulation group (0 when first_micro, else the previous
+ * row's + 1), a cleared optimizer part, the Bn timesteps (device int64, exact in f32) and the Bn per-sample losses (of
+ * vneti_mse_loss_per_sample) — and then advances the counter.  Row layout (floats): */
+#define VNETI_TELEMETRY_SEQ 0
+#define VNETI_TELEMETRY_MICRO 1
+#define VNETI_TELEMETRY_CLOSED 2
+#define VNETI_TELEMETRY_NORM_OBJECT 3
+#define VNETI_TELEMETRY_NORM_VIEW 4
+#define VNETI_TELEMETRY_NORM_TOTAL 5
+#define VNETI_TELEMETRY_FINITE 6
+#define VNETI_TELEMETRY_CLIP_COEF 7
+#define VNETI_TELEMETRY_LOSS_SCALE 8
+#define VNETI_TELEMETRY_LR 9
+#define VNETI_TELEMETRY_HEADER 10 /* then timesteps[Bn], losses[Bn] */
+int vneti_train_record(float* ring, int* count, int rows, int row_floats, int first_micro, const void* timesteps_i64,
+                       const float* losses, int Bn, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * NeTI text path

@@ -128,7 +128,13 @@ class Coach:
             unconstrained_object=m.bypass_unconstrained_object, unconstrained_view=m.bypass_unconstrained_view,
             nested_dropout_prob=m.nested_dropout_prob if m.use_nested_dropout else 0.0,
             moment_cache_images=0 if forward_only else self._moment_cache_size(), need_backward=not forward_only,
-            **first.engine_encoder_kwargs(), **kw)
+            max_grad_norm=None if forward_only else cfg.optim.max_grad_norm,
+            telemetry_rows=self._telemetry_rows(), **first.engine_encoder_kwargs(), **kw)
+        # per-step record (extension): every rank records (one launch list for all), rank 0 writes the file
+        self.metrics = None
+        if self._telemetry_rows() and self.rank == 0:
+            from .train_metrics import TrainMetricsFile
+            self.metrics = TrainMetricsFile(cfg.log.exp_dir, self.start_step)
         if self._trainer_state is not None:
             resume.check_fingerprint(self._trainer_state["fingerprint"], self._fingerprint(self.engine.params.numel()))
             self.engine.load_state_dict(self._trainer_state.pop("engine"))
@@ -224,7 +230,29 @@ class Coach:
     def _fingerprint(self, n_params: Optional[int] = None):
         cfg = self.cfg
         return resume.fingerprint(cfg.learnable_mode, cfg.optim.train_batch_size, cfg.optim.gradient_accumulation_steps,
-                                  self.world, cfg.optim.mixed_precision, cfg.seed, len(self.train_dataset), n_params)
+                                  self.world, cfg.optim.mixed_precision, cfg.seed, len(self.train_dataset), n_params,
+                                  max_grad_norm=cfg.optim.max_grad_norm)
+
+    def _telemetry_rows(self) -> int:
+        """the ring holds twice the micro-steps between two reads (the loop reads it at every 50th optimizer step)"""
+        if not self.cfg.log.train_metrics or self.forward_only:
+            return 0
+        from ..engine.telemetry import default_rows
+        from .train_metrics import LOG_EVERY
+        return default_rows(LOG_EVERY, self.cfg.optim.gradient_accumulation_steps)
+
+    def _flush_metrics(self, global_step: int):
+        """fetch the record (one copy + sync: only called where the loop syncs anyway) and append the optimizer steps up
+        to `global_step` to train-metrics.jsonl"""
+        if self.metrics is None:
+            return
+        from .train_metrics import group_rows, lines_up_to
+        rows, lost = self.engine.read_telemetry()
+        groups, _, dropped = group_rows(rows)
+        if lost or dropped:
+            self.log(f"WARNING: train metrics: {lost} micro-step(s) overwritten in the ring before they were read, "
+                     f"{dropped} more dropped with their group")
+        self.metrics.append(lines_up_to(groups, global_step, omit_object=self.mapper_object_lookup is None))
 
     def _load_resume_mappers(self, directory=None, step: Optional[int] = None):
         """the mappers this run TRAINS take their weights from the checkpoint pair (a frozen view mapper, modes 4 / 5,
@@ -271,6 +299,7 @@ class Coach:
         RNG state only."""
         out = Path(self.cfg.log.exp_dir)
         host = resume.capture_host_state(self.batch_sampler, self.train_dataset, self._loader_generator)
+        self._flush_metrics(step)  # (the state's .cpu() copies below sync anyway) the file then holds every step <= N
         if self.rank > 0:
             resume.atomic_save({"format": resume.FORMAT, "step": step, "host": host,
                                 "rng_state": self.engine.rng_state.cpu()}, resume.state_file(out, step, self.rank))
@@ -532,7 +561,14 @@ class Coach:
                     if not self.lr_schedule.constant:
                         eng.set_lr(self.lr_schedule.lr(global_step))  # device scalar: no re-capture
                     if global_step % 50 == 0 or global_step == 1:
-                        self.log(f"step {global_step} loss {eng.loss():.5f} lr {float(eng.hyper[0]):.2e} "
+                        self._flush_metrics(global_step)
+                        extra = ""
+                        if self.metrics is not None and self.metrics.last is not None:
+                            last = self.metrics.last
+                            norm = last["grad_norm"]["total"]
+                            extra = (f" grad_norm {'nan' if norm is None else format(norm, '.3e')} "
+                                     f"loss_scale {last['loss_scale']:g}")
+                        self.log(f"step {global_step} loss {eng.loss():.5f} lr {float(eng.hyper[0]):.2e}{extra} "
                                  f"{(global_step - self.start_step) / (time.time() - t0):.2f} it/s")
                     if global_step % cfg.log.save_steps == 0:
                         self.save(f"learned_embeds-steps-{global_step}.bin", f"mapper-steps-{global_step}.pt")
@@ -546,4 +582,5 @@ class Coach:
                 if global_step >= cfg.optim.max_train_steps:
                     break
         torch.cuda.synchronize()
+        self._flush_metrics(global_step)
         self.save("learned_embeds-final.bin", "mapper-final.pt")

@@ -54,6 +54,11 @@ class LogConfig:
     keep_trainer_states: int = field(default=2, metadata={"ext": True, "run_control": True})
     # continue from the newest complete state in exp_dir
     auto_resume: bool = field(default=False, metadata={"ext": True, "run_control": True})
+    # per-step training record (the reference logs total_loss and lr to its tracker after every micro-step,
+    # coach.py:256-261): rank 0 appends one line per optimizer step to <exp_dir>/train-metrics.jsonl — loss, lr, loss
+    # scale, skipped steps, gradient norms, clip coefficient and every sample's (timestep, loss) — produced on the device
+    # inside the captured step and fetched where the loop already syncs (compat/train_metrics.py)
+    train_metrics: bool = field(default=False, metadata={"ext": True, "run_control": True})
 
 
 @dataclass
@@ -212,6 +217,15 @@ class OptimConfig:
     adam_epsilon: float = 1e-08
     mixed_precision: str = "no"
     allow_tf32: bool = False
+    # extension: clip the mappers' global gradient norm before AdamW, accelerator.clip_grad_norm_ /
+    # torch.nn.utils.clip_grad_norm_ semantics.  It describes the trained model (not run control): it travels beside a
+    # checkpoint's cfg and enters the resume fingerprint — where it is set ("when_set": config.yaml and a checkpoint's
+    # extension fields of a run without it are the ones they always were)
+    max_grad_norm: Optional[float] = field(default=None, metadata={"ext": True, "when_set": True})
+
+    def __post_init__(self):
+        if self.max_grad_norm is not None and not self.max_grad_norm > 0:
+            raise ValueError(f"optim.max_grad_norm must be > 0 when set (is {self.max_grad_norm})")
 
 
 @dataclass
@@ -254,7 +268,7 @@ def encode(obj, include_ext: bool = True):
     if is_dataclass(obj) and not isinstance(obj, type):
         return {f.name: encode(getattr(obj, f.name), include_ext) for f in fields(obj)
                 if (include_ext or not f.metadata.get("ext"))
-                and not (f.metadata.get("run_control") and getattr(obj, f.name) == f.default)}
+                and not ((f.metadata.get("run_control") or f.metadata.get("when_set")) and getattr(obj, f.name) == f.default)}
     if isinstance(obj, Path):
         return str(obj)
     if isinstance(obj, dict):
@@ -272,7 +286,8 @@ def ext_fields(obj) -> Dict[str, Any]:
         v = getattr(obj, f.name)
         if is_dataclass(v):
             out.update({f"{f.name}.{k}": x for k, x in ext_fields(v).items()})
-        elif f.metadata.get("ext") and not f.metadata.get("run_control"):
+        elif f.metadata.get("ext") and not f.metadata.get("run_control") \
+                and not (f.metadata.get("when_set") and v == f.default):
             out[f.name] = v
     return out
 

@@ -235,17 +235,24 @@ def prune_states(directory, keep: int) -> List[Path]:
 
 # ---------------------------------------------------------------------------------------------- fingerprint
 def fingerprint(learnable_mode: int, batch_size: int, grad_accum: int, world: int, precision: str, seed: Optional[int],
-                dataset_len: int, n_params: Optional[int] = None) -> Dict[str, Any]:
+                dataset_len: int, n_params: Optional[int] = None, max_grad_norm: Optional[float] = None) -> Dict[str, Any]:
     fp = {"learnable_mode": int(learnable_mode), "train_batch_size": int(batch_size),
           "gradient_accumulation_steps": int(grad_accum), "world_size": int(world), "precision": str(precision),
           "seed": -1 if seed is None else int(seed), "dataset_len": int(dataset_len)}
     if n_params is not None:
         fp["n_params"] = int(n_params)
+    if max_grad_norm is not None:  # only when set: the fingerprint of an unclipped run is the one it always was
+        fp["max_grad_norm"] = float(max_grad_norm)
     return fp
+
+
+# fields that are present only where they are set: absent on one side and present on the other is a difference too
+_WHEN_SET = ("max_grad_norm",)
 
 
 def check_fingerprint(saved: Dict[str, Any], current: Dict[str, Any]):
     """raises a ValueError that lists every field of `current` the saved state disagrees with"""
     diff = [f"{k}: saved {saved.get(k)!r}, this run {v!r}" for k, v in current.items() if saved.get(k) != v]
+    diff += [f"{k}: saved {saved[k]!r}, this run None" for k in _WHEN_SET if k in saved and k not in current]
     if diff:
         raise ValueError("this run cannot continue the saved trainer state; they differ in " + "; ".join(diff))

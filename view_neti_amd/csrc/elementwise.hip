@@ -484,14 +484,20 @@ __global__ __launch_bounds__(256) void grads_check_finite_kernel(const float* g,
   }
   if (__any(bad) && (threadIdx.x & 63) == 0) scaler[2] = 1.f;
 }
+// CLIP (the _clipped entries): the unscaled gradient is multiplied by clip[0], torch.nn.utils.clip_grad_norm_'s
+// `g.mul_(clip_coef_clamped)` — always, also when the coefficient is 1 (then it changes no bit).  CLIP = false is the body
+// the unclipped entries always had: `clip` is never read.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, float* m, float* v, long long n,
-                                                    const float* hyper, const float* scaler, const int* step) {
+                                                    const float* hyper, const float* scaler, const int* step,
+                                                    const float* clip) {
   long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
   if (gid >= n) return;
   if (scaler[2] != 0.f) return;  // GradScaler.step(): skip the update when grads are non-finite
   const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], gdiv = hyper[5];
   const int t = step[0] + 1;
   float grad = g[gid] / (scaler[0] * gdiv);
+  if constexpr (CLIP) grad *= clip[0];
   float pv = p[gid] * (1.f - lr * wd);
   float mv = b1 * m[gid] + (1.f - b1) * grad;
   float vv = b2 * v[gid] + (1.f - b2) * grad * grad;
@@ -505,10 +511,11 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, fl
 // a segment joins the update set the first time it receives a gradient (grad None -> skipped,
 // torch/optim/adamw.py) and from then on is stepped every iteration, with a zero gradient when it
 // was not in the batch (zero_grad() keeps zero tensors in torch 1.13), each with its own `step`.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void adamw_segments_kernel(float* p, const float* g, float* m, float* v,
                                                              long long n, long long seg_len, const int* seg_step,
                                                              const int* active, int n_active, const float* hyper,
-                                                             const float* scaler) {
+                                                             const float* scaler, const float* clip) {
   long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
   if (gid >= n) return;
   if (scaler[2] != 0.f) return;
@@ -520,6 +527,7 @@ __global__ __launch_bounds__(256) void adamw_segments_kernel(float* p, const flo
   const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], gdiv = hyper[5];
   const int t = t0 + 1;
   float grad = is_active ? g[gid] / (scaler[0] * gdiv) : 0.f;
+  if constexpr (CLIP) grad *= clip[0];
   float pv = p[gid] * (1.f - lr * wd);
   float mv = b1 * m[gid] + (1.f - b1) * grad;
   float vv = b2 * v[gid] + (1.f - b2) * grad * grad;
@@ -566,6 +574,113 @@ __global__ void scaler_update_kernel(float* scaler, int* step, int growth_interv
     }
   }
   scaler[2] = 0.f;
+}
+
+// ---- gradient norm (clipping, per-step record) --------------------------------------------------
+// Sum of squares of an f32 gradient bucket in two stages, in a FIXED order and without float atomics (as
+// mse_per_sample_kernel): block (chunk, s) owns the kGradChunk floats [chunk * kGradChunk, ...) of segment s — the flat
+// range when `active` is null, else segment active[s] of length `len` (grads_check_finite_segments_kernel's addressing) —
+// thread t adds the squares of elements t, t + 256, ... in that order, then the LDS tree; ws[s * nchunk + chunk] is the
+// partial.  Squares and sums are f64: (3.4e38)^2 = 1.2e77 is a finite double, so the total is non-finite exactly when an
+// element is.  Scalar loads: the view mapper's range starts wherever the object mappers end, no alignment holds.  The
+// bucket is ~0.5 MiB per mapper: the launch is the cost, not the bytes.
+constexpr int kGradChunk = 4096;
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, long long len,
+                                                         const int* __restrict__ active, double* __restrict__ ws,
+                                                         int nchunk) {
+  __shared__ double red[256];
+  const int chunk = blockIdx.x, s = blockIdx.y, t = threadIdx.x;
+  const float* base = g + (active ? (long long)active[s] * len : 0LL);
+  const long long lo = (long long)chunk * kGradChunk;
+  double acc = 0.0;
+#pragma unroll 4
+  for (int j = 0; j < kGradChunk / 256; ++j) {
+    const long long i = lo + j * 256 + t;
+    if (i < len) {
+      const double x = (double)base[i];
+      acc = fma(x, x, acc);
+    }
+  }
+  red[t] = acc;
+  __syncthreads();
+#pragma unroll
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) red[t] += red[t + w];
+    __syncthreads();
+  }
+  if (t == 0) ws[(long long)s * nchunk + chunk] = red[0];
+}
+// One block: the partials of the object side, then of the view side, added in index order in f64 (either side may be
+// absent: its norm reads -1).  out = {norm_object, norm_view, norm_total, finite, clip_coef}, norms of the UNSCALED mean
+// gradient: sqrt(sum) / (scaler[0] * hyper[5]).  clip_coef = min(1, max_norm / (norm_total + 1e-6)) in f32, torch's
+// clip_grad_norm_; exactly 1 when max_norm[0] <= 0 (clipping off) or the sum is non-finite (the step is skipped anyway).
+// ring (optional): the same values, the loss scale and the lr go into the row of the micro-step that closed the group,
+// (count[0] - 1) % rows, with its "closed a group" flag.
+__global__ __launch_bounds__(64) void grad_norm_finish_kernel(const double* __restrict__ ws_o, int n_o,
+                                                              const double* __restrict__ ws_v, int n_v,
+                                                              const float* __restrict__ scaler,
+                                                              const float* __restrict__ hyper,
+                                                              const float* __restrict__ max_norm, float* __restrict__ out,
+                                                              float* __restrict__ ring, const int* __restrict__ count,
+                                                              int rows, int row_floats) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double so = 0.0, sv = 0.0;
+  for (int k = 0; k < n_o; ++k) so += ws_o[k];
+  for (int k = 0; k < n_v; ++k) sv += ws_v[k];
+  const double tot = so + sv;
+  const float scale = scaler[0];
+  const double div = (double)(scale * hyper[5]);
+  const float no = n_o > 0 ? (float)(sqrt(so) / div) : -1.f;
+  const float nv = n_v > 0 ? (float)(sqrt(sv) / div) : -1.f;
+  const float nt = (float)(sqrt(tot) / div);
+  const bool finite = tot == tot && tot != (double)INFINITY;
+  const float mx = max_norm[0];
+  float coef = 1.f;
+  if (finite && mx > 0.f) coef = fminf(1.f, mx / (nt + 1e-6f));
+  out[0] = no;
+  out[1] = nv;
+  out[2] = nt;
+  out[3] = finite ? 1.f : 0.f;
+  out[4] = coef;
+  if (ring) {
+    const int c = count[0];
+    if (c > 0) {
+      float* row = ring + (long long)((unsigned)(c - 1) % (unsigned)rows) * row_floats;
+      row[VNETI_TELEMETRY_CLOSED] = 1.f;
+      row[VNETI_TELEMETRY_NORM_OBJECT] = no;
+      row[VNETI_TELEMETRY_NORM_VIEW] = nv;
+      row[VNETI_TELEMETRY_NORM_TOTAL] = nt;
+      row[VNETI_TELEMETRY_FINITE] = finite ? 1.f : 0.f;
+      row[VNETI_TELEMETRY_CLIP_COEF] = coef;
+      row[VNETI_TELEMETRY_LOSS_SCALE] = scale;
+      row[VNETI_TELEMETRY_LR] = hyper[0];
+    }
+  }
+}
+// The micro-step's part of ring row count[0] % rows: sequence number (count mod 2^24, exact in f32: a reader tells the
+// laps of the ring apart by it), micro index (0 when `first`, else the previous row's + 1), a cleared "closed a group"
+// part, the Bn timesteps and per-sample losses.  Then count[0] += 1.  One block; every thread reads the counter before the
+// barrier, thread 0 advances it after.
+__global__ __launch_bounds__(256) void train_record_kernel(float* __restrict__ ring, int* __restrict__ count, int rows,
+                                                           int row_floats, int first, const long long* __restrict__ t,
+                                                           const float* __restrict__ losses, int Bn) {
+  const int c = count[0];
+  const unsigned r = (unsigned)c % (unsigned)rows, rp = (unsigned)(c + rows - 1) % (unsigned)rows;
+  float* row = ring + (long long)r * row_floats;
+  const float prev_micro = ring[(long long)rp * row_floats + VNETI_TELEMETRY_MICRO];
+  __syncthreads();  // rows == 1: the previous row is this one
+  for (int i = threadIdx.x; i < VNETI_TELEMETRY_HEADER; i += 256) {
+    float x = 0.f;
+    if (i == VNETI_TELEMETRY_SEQ) x = (float)(c & 0xFFFFFF);
+    if (i == VNETI_TELEMETRY_MICRO) x = first ? 0.f : prev_micro + 1.f;
+    row[i] = x;
+  }
+  for (int b = threadIdx.x; b < Bn; b += 256) {
+    row[VNETI_TELEMETRY_HEADER + b] = (float)t[b];
+    row[VNETI_TELEMETRY_HEADER + Bn + b] = losses[b];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) count[0] = c + 1;
 }
 
 }  // namespace
@@ -825,35 +940,119 @@ extern "C" int vneti_mse_loss_per_sample(const void* pred, long long ldp, const 
   return vneti_check_launch("mse_loss_per_sample_finish");
 }
 
+static int adamw_segments_launch(const char* what, float* p, const float* g, float* m, float* v, long long seg_len,
+                                 int n_seg, int* seg_step, const int* active, int n_active, const float* hyper,
+                                 float* scaler, int* step, int growth_interval, int phases, const float* clip,
+                                 void* stream) {
+  const long long n = seg_len * n_seg;
+  if (phases & 1)
+    hipLaunchKernelGGL(grads_check_finite_segments_kernel, dim3((unsigned)cdivl(seg_len, 256), n_active), dim3(256),
+                       0, ST, g, seg_len, active, scaler);
+  if (phases & 2) {
+    if (clip)
+      hipLaunchKernelGGL(adamw_segments_kernel<true>, dim3((unsigned)cdivl(n, 256)), dim3(256), 0, ST, p, g, m, v, n,
+                         seg_len, (const int*)seg_step, active, n_active, hyper, (const float*)scaler, clip);
+    else
+      hipLaunchKernelGGL(adamw_segments_kernel<false>, dim3((unsigned)cdivl(n, 256)), dim3(256), 0, ST, p, g, m, v, n,
+                         seg_len, (const int*)seg_step, active, n_active, hyper, (const float*)scaler,
+                         (const float*)nullptr);
+    hipLaunchKernelGGL(segments_step_kernel, dim3(cdiv(n_seg, 256)), dim3(256), 0, ST, seg_step, n_seg, active,
+                       n_active, (const float*)scaler);
+  }
+  if (phases & 4) hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(64), 0, ST, scaler, step, growth_interval);
+  return vneti_check_launch(what);
+}
+
 extern "C" int vneti_adamw_segments(float* p, const float* g, float* m, float* v, long long seg_len, int n_seg,
                                     int* seg_step, const int* active, int n_active, const float* hyper,
                                     float* scaler, int* step, int growth_interval, int phases, void* stream) {
   VN_REQUIRE(p && g && m && v && hyper && scaler && step && seg_step && active && seg_len > 0 && n_seg > 0 &&
                  n_active > 0 && n_active <= 8 && phases > 0 && phases < 8,
              "adamw_segments: bad arguments");
-  const long long n = seg_len * n_seg;
-  if (phases & 1)
-    hipLaunchKernelGGL(grads_check_finite_segments_kernel, dim3((unsigned)cdivl(seg_len, 256), n_active), dim3(256),
-                       0, ST, g, seg_len, active, scaler);
+  return adamw_segments_launch("adamw_segments", p, g, m, v, seg_len, n_seg, seg_step, active, n_active, hyper, scaler,
+                               step, growth_interval, phases, nullptr, stream);
+}
+
+extern "C" int vneti_adamw_segments_clipped(float* p, const float* g, float* m, float* v, long long seg_len, int n_seg,
+                                            int* seg_step, const int* active, int n_active, const float* hyper,
+                                            float* scaler, int* step, int growth_interval, int phases,
+                                            const float* clip_coef, void* stream) {
+  VN_REQUIRE(p && g && m && v && hyper && scaler && step && seg_step && active && clip_coef && seg_len > 0 && n_seg > 0 &&
+                 n_active > 0 && n_active <= 8 && phases > 0 && phases < 8,
+             "adamw_segments_clipped: bad arguments");
+  return adamw_segments_launch("adamw_segments_clipped", p, g, m, v, seg_len, n_seg, seg_step, active, n_active, hyper,
+                               scaler, step, growth_interval, phases, clip_coef, stream);
+}
+
+static int adamw_flat_launch(const char* what, float* p, const float* g, float* m, float* v, long long n,
+                             const float* hyper, float* scaler, int* step, int growth_interval, int phases,
+                             const float* clip, void* stream) {
+  unsigned blocks = (unsigned)cdivl(n, 256);
+  if (phases & 1) hipLaunchKernelGGL(grads_check_finite_kernel, dim3(blocks), dim3(256), 0, ST, g, n, scaler);
   if (phases & 2) {
-    hipLaunchKernelGGL(adamw_segments_kernel, dim3((unsigned)cdivl(n, 256)), dim3(256), 0, ST, p, g, m, v, n, seg_len,
-                       (const int*)seg_step, active, n_active, hyper, (const float*)scaler);
-    hipLaunchKernelGGL(segments_step_kernel, dim3(cdiv(n_seg, 256)), dim3(256), 0, ST, seg_step, n_seg, active,
-                       n_active, (const float*)scaler);
+    if (clip)
+      hipLaunchKernelGGL(adamw_kernel<true>, dim3(blocks), dim3(256), 0, ST, p, g, m, v, n, hyper, (const float*)scaler,
+                         (const int*)step, clip);
+    else
+      hipLaunchKernelGGL(adamw_kernel<false>, dim3(blocks), dim3(256), 0, ST, p, g, m, v, n, hyper, (const float*)scaler,
+                         (const int*)step, (const float*)nullptr);
   }
   if (phases & 4) hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(64), 0, ST, scaler, step, growth_interval);
-  return vneti_check_launch("adamw_segments");
+  return vneti_check_launch(what);
 }
 
 extern "C" int vneti_adamw_flat(float* p, const float* g, float* m, float* v, long long n, const float* hyper,
                                 float* scaler, int* step, int growth_interval, int phases, void* stream) {
   VN_REQUIRE(p && g && m && v && hyper && scaler && step && n > 0 && phases > 0 && phases < 8,
              "adamw_flat: bad arguments");
-  unsigned blocks = (unsigned)cdivl(n, 256);
-  if (phases & 1) hipLaunchKernelGGL(grads_check_finite_kernel, dim3(blocks), dim3(256), 0, ST, g, n, scaler);
-  if (phases & 2)
-    hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, ST, p, g, m, v, n, hyper, (const float*)scaler,
-                       (const int*)step);
-  if (phases & 4) hipLaunchKernelGGL(scaler_update_kernel, dim3(1), dim3(64), 0, ST, scaler, step, growth_interval);
-  return vneti_check_launch("adamw_flat");
+  return adamw_flat_launch("adamw_flat", p, g, m, v, n, hyper, scaler, step, growth_interval, phases, nullptr, stream);
+}
+
+extern "C" int vneti_adamw_flat_clipped(float* p, const float* g, float* m, float* v, long long n, const float* hyper,
+                                        float* scaler, int* step, int growth_interval, int phases, const float* clip_coef,
+                                        void* stream) {
+  VN_REQUIRE(p && g && m && v && hyper && scaler && step && clip_coef && n > 0 && phases > 0 && phases < 8,
+             "adamw_flat_clipped: bad arguments");
+  return adamw_flat_launch("adamw_flat_clipped", p, g, m, v, n, hyper, scaler, step, growth_interval, phases, clip_coef,
+                           stream);
+}
+
+extern "C" long long vneti_grad_sumsq_ws_doubles(long long len, int n_active) {
+  if (len <= 0 || n_active < 0 || n_active > 8 || cdivl(len, kGradChunk) > 0x7fffffLL) return -1;
+  return cdivl(len, kGradChunk) * (n_active > 0 ? n_active : 1);
+}
+
+extern "C" int vneti_grad_sumsq(const float* g, long long len, const int* active, int n_active, void* ws, void* stream) {
+  VN_REQUIRE(g && ws && len > 0, "grad_sumsq: bad arguments");
+  VN_REQUIRE(active ? (n_active > 0 && n_active <= 8) : n_active == 0,
+             "grad_sumsq: n_active=%d (1..8 segment ids with `active`, 0 for the flat range without)", n_active);
+  const long long nchunk = cdivl(len, kGradChunk);
+  VN_REQUIRE(nchunk <= 0x7fffffLL, "grad_sumsq: %lld floats is more than one launch covers", len);
+  VN_REQUIRE(((uintptr_t)ws & 7u) == 0, "grad_sumsq: the f64 workspace must be 8-byte aligned");
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)nchunk, active ? n_active : 1), dim3(256), 0, ST, g, len, active,
+                     (double*)ws, (int)nchunk);
+  return vneti_check_launch("grad_sumsq");
+}
+
+extern "C" int vneti_grad_norm_finish(const void* ws_object, long long n_object, const void* ws_view, long long n_view,
+                                      const float* scaler, const float* hyper, const float* max_norm, float* out,
+                                      float* ring, const int* count, int rows, int row_floats, void* stream) {
+  VN_REQUIRE(scaler && hyper && max_norm && out && n_object >= 0 && n_view >= 0 && n_object + n_view > 0 &&
+                 n_object < 0x7fffffffLL && n_view < 0x7fffffffLL && (n_object == 0 || ws_object) && (n_view == 0 || ws_view),
+             "grad_norm_finish: bad arguments");
+  VN_REQUIRE(!ring || (count && rows > 0 && row_floats >= VNETI_TELEMETRY_HEADER),
+             "grad_norm_finish: a telemetry ring needs its counter, rows > 0 and row_floats >= %d", VNETI_TELEMETRY_HEADER);
+  hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(64), 0, ST, (const double*)ws_object, (int)n_object,
+                     (const double*)ws_view, (int)n_view, scaler, hyper, max_norm, out, ring, count, rows, row_floats);
+  return vneti_check_launch("grad_norm_finish");
+}
+
+extern "C" int vneti_train_record(float* ring, int* count, int rows, int row_floats, int first_micro,
+                                  const void* timesteps_i64, const float* losses, int Bn, void* stream) {
+  VN_REQUIRE(ring && count && timesteps_i64 && losses && rows > 0 && Bn > 0, "train_record: bad arguments");
+  VN_REQUIRE(row_floats == VNETI_TELEMETRY_HEADER + 2 * Bn, "train_record: row_floats=%d, a row of Bn=%d samples has %d",
+             row_floats, Bn, VNETI_TELEMETRY_HEADER + 2 * Bn);
+  hipLaunchKernelGGL(train_record_kernel, dim3(1), dim3(256), 0, ST, ring, count, rows, row_floats, first_micro,
+                     (const long long*)timesteps_i64, losses, Bn);
+  return vneti_check_launch("train_record");
 }

@@ -53,10 +53,14 @@ class TrainStepEngine:
                  nested_dropout_prob: float = 0.0, hidden_object: int = 64,
                  legacy_pe_object: Optional[torch.Tensor] = None, enc_dim_object: int = 64,
                  output_bypass_object: bool = True, output_bypass_view: bool = True, exchange=None,
-                 moment_cache_images: int = 0):
+                 moment_cache_images: int = 0, max_grad_norm: Optional[float] = None, telemetry_rows: int = 0):
         """mapper_object: one mapper state_dict, or a list of them (learnable_mode 3: one object mapper per
         scene, `mapper_object_lookup`, training/coach.py:505-552) — `set_batch(object_index=k)` picks the one
-        the batch trains."""
+        the batch trains.
+        max_grad_norm: clip the (unscaled, mean) mapper gradient to this global L2 norm before AdamW, as
+        torch.nn.utils.clip_grad_norm_ after GradScaler.unscale_ would.  telemetry_rows: > 0 keeps a device ring of that
+        many micro-steps (timesteps, per-sample losses, gradient norms, loss scale, lr, skipped steps) for
+        read_telemetry().  Both off: the step enqueues the launches it always did."""
         from .text import flatten_mapper_state
         self.cfg = cfg
         self.B, self.H, self.W = batch, height, width
@@ -192,6 +196,37 @@ class TrainStepEngine:
         self.micro = 0
         self._eval_batch = False  # the current batch was set for eval_losses(): not to be trained on
         self.n_loss = batch * Lc * self.h * self.w
+        # ---- gradient norm / clipping / per-step record.  None of it is trainer state
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"max_grad_norm must be > 0 (is {max_grad_norm!r}); None turns clipping off")
+        if telemetry_rows < 0 or (telemetry_rows and not need_backward):
+            raise ValueError("telemetry_rows must be >= 0, and the record needs an engine that trains")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.telemetry_rows = int(telemetry_rows)
+        self._norm_path = self.max_grad_norm is not None or self.telemetry_rows > 0
+        self._ephemeral = ()  # what _capture() snapshots and restores besides the trainer state
+        if self._norm_path:
+            multi_obj = self.n_objects > 1
+            n_view = self.params.numel() - n_all_obj
+            self.max_norm_dev = torch.tensor([self.max_grad_norm or 0.0], dtype=torch.float32, device=device)
+            self.norm_out = torch.zeros(ops.NORM_OUT_FLOATS, dtype=torch.float32, device=device)
+            self._n_ws_obj = ops.grad_sumsq_ws_doubles(self.n_obj, 1) if multi_obj else ops.grad_sumsq_ws_doubles(n_all_obj)
+            self._n_ws_view = ops.grad_sumsq_ws_doubles(n_view) if n_view else 0
+            self.norm_ws_obj = torch.zeros(self._n_ws_obj, dtype=torch.float64, device=device)
+            self.norm_ws_view = torch.zeros(self._n_ws_view, dtype=torch.float64, device=device) if n_view else None
+            self._ephemeral = (self.norm_out,)
+        self.tele_ring = self.tele_count = None
+        if self.telemetry_rows:
+            # ONE buffer [counter, 3 x pad | ring]: read_telemetry() is one device -> host copy
+            W = ops.telemetry_row_floats(batch)
+            self.tele_buf = torch.zeros(4 + self.telemetry_rows * W, dtype=torch.int32, device=device)
+            self.tele_count = self.tele_buf[0:1]
+            self.tele_ring = self.tele_buf[4:].view(torch.float32)
+            self.rec_loss = torch.zeros(batch, dtype=torch.float32, device=device)
+            self.rec_ws = torch.zeros_like(self.eval_ws)
+            self._tele_read = 0       # the counter at the last read_telemetry()
+            self.telemetry_lost = 0   # micro-steps overwritten before they were read, over the engine's life
+            self._ephemeral += (self.tele_buf,)
 
     # ------------------------------------------------------------------ inputs
     def set_batch(self, pixel_values, input_ids, placeholder_object, placeholder_view=None, view_params=None,
@@ -261,7 +296,8 @@ class TrainStepEngine:
         from .. import lib
         return {"n_params": self.params.numel(), "n_objects": self.n_objects, "n_obj": self.n_obj,
                 "view_in_bucket": self.params.numel() > self.n_all_obj, "grad_accum": self.grad_accum,
-                "world_size": self.world_size, "precision": lib.precision()}
+                "world_size": self.world_size, "precision": lib.precision(),
+                **({"max_grad_norm": self.max_grad_norm} if self.max_grad_norm is not None else {})}
 
     def state_dict(self) -> Dict:
         """CPU copies of everything the captured step reads and writes in place — the set `_capture` snapshots around its
@@ -283,6 +319,8 @@ class TrainStepEngine:
             raise RuntimeError("load_state_dict() inside a gradient-accumulation group")
         want, have = self._describe(), sd.get("meta", {})
         bad = [f"{k}: saved {have.get(k)!r}, this engine {v!r}" for k, v in want.items() if have.get(k) != v]
+        if "max_grad_norm" in have and "max_grad_norm" not in want:  # (a state from before f7 has no such key: unclipped)
+            bad.append(f"max_grad_norm: saved {have['max_grad_norm']!r}, this engine None")
         bad += [f"{name}: saved shape {tuple(sd[name].shape) if name in sd else None}, this engine "
                 f"{tuple(getattr(self, name).shape)}" for name in self._STATE
                 if name not in sd or sd[name].shape != getattr(self, name).shape or sd[name].dtype != getattr(self, name).dtype]
@@ -306,6 +344,10 @@ class TrainStepEngine:
         self._forward_half(cached, bool(self.n_cache), fork=self.overlap)
         self.loss_sum.zero_()
         ops.mse_loss_grad(self.unet.pred, self.target, self.unet.dpred, self.loss_sum, self.scaler, B, Lc, hw)
+        if self.telemetry_rows:  # the micro-step's row: timesteps + the deterministic per-sample losses, then count += 1
+            ops.mse_loss_per_sample(self.unet.pred, self.target, self.rec_loss, self.rec_ws, B, Lc, hw)
+            ops.train_record(self.tele_ring, self.tele_count, self.telemetry_rows, not accumulate, self.timesteps,
+                             self.rec_loss, B)
         if self.need_backward:
             self.unet.backward()
             self.text.backward()
@@ -342,10 +384,33 @@ class TrainStepEngine:
             self.unet.forward_pre()
         self.unet.forward_main()
 
+    def _grad_norm(self):
+        """sum of squares of the object side (the whole object range, or the active segment of several) and of the view
+        side, then one finish launch: norms, finite flag and clip coefficient into norm_out, and the optimizer's part of
+        the ring row of the micro-step that closed the group.  After all_reduce(): every rank computes the same norm."""
+        no = self.n_all_obj
+        if self.n_objects > 1:
+            ops.grad_sumsq(self.grads[:no], self.norm_ws_obj, seg_len=self.n_obj, active=self.obj_slot)
+        else:
+            ops.grad_sumsq(self.grads[:no], self.norm_ws_obj)
+        if self._n_ws_view:
+            ops.grad_sumsq(self.grads[no:], self.norm_ws_view)
+        ops.grad_norm_finish(self.norm_ws_obj, self._n_ws_obj, self.norm_ws_view, self._n_ws_view, self.scaler, self.hyper,
+                             self.max_norm_dev, self.norm_out, self.tele_ring, self.tele_count, self.telemetry_rows,
+                             ops.telemetry_row_floats(self.B) if self.telemetry_rows else 0)
+
     def optimizer_step(self):
-        a = (self.hyper, self.scaler, self.opt_step, self.growth_interval)
+        a = (self.hyper, self.scaler, self.opt_step)
+        kw = dict(growth_interval=self.growth_interval)
+        flat, segments = ops.adamw_flat, ops.adamw_segments
+        if self._norm_path:
+            self._grad_norm()
+        if self.max_grad_norm is not None:
+            # the same calls in the same CHECK / APPLY / FINISH order, gradient times the clip coefficient (a device scalar)
+            a += (self.norm_out[ops.NORM_CLIP_COEF:],)
+            flat, segments = ops.adamw_flat_clipped, ops.adamw_segments_clipped
         if self.n_objects == 1:
-            ops.adamw_flat(self.params, self.grads, self.exp_avg, self.exp_avg_sq, *a)
+            flat(self.params, self.grads, self.exp_avg, self.exp_avg_sq, *a, **kw)
             return
         # several buckets, one optimizer step: check all, apply all, then GradScaler.update once
         no = self.n_all_obj
@@ -354,11 +419,28 @@ class TrainStepEngine:
         view = (self.params[no:], self.grads[no:], self.exp_avg[no:], self.exp_avg_sq[no:])
         has_view = self.params.numel() > no
         if has_view:
-            ops.adamw_flat(*view, *a, phases=ops.OPT_CHECK)
-        ops.adamw_segments(*obj, *a, phases=ops.OPT_CHECK)
+            flat(*view, *a, phases=ops.OPT_CHECK, **kw)
+        segments(*obj, *a, phases=ops.OPT_CHECK, **kw)
         if has_view:
-            ops.adamw_flat(*view, *a, phases=ops.OPT_APPLY)
-        ops.adamw_segments(*obj, *a, phases=ops.OPT_APPLY | ops.OPT_FINISH)
+            flat(*view, *a, phases=ops.OPT_APPLY, **kw)
+        segments(*obj, *a, phases=ops.OPT_APPLY | ops.OPT_FINISH, **kw)
+
+    # ------------------------------------------------------------------ per-step record
+    def read_telemetry(self):
+        """the micro-steps recorded since the last read, oldest first: (rows, lost).  One device -> host copy and sync.  A
+        row is a dict {micro_step, micro, timesteps[B], losses[B], closed}; the row of the micro-step that closed an
+        accumulation group also has skipped, clip_coef, loss_scale, lr and grad_norm {total, object?, view?}.  lost: the
+        micro-steps the ring had already overwritten (more than telemetry_rows since the last read)."""
+        if not self.telemetry_rows:
+            raise RuntimeError("read_telemetry(): this engine was built with telemetry_rows=0")
+        from .telemetry import decode_ring
+        host = self.tele_buf.cpu()
+        count = int(host[0])
+        ring = host[4:].view(torch.float32).view(self.telemetry_rows, -1)
+        rows, lost = decode_ring(ring, count, min(self._tele_read, count), self.B)
+        self._tele_read = count
+        self.telemetry_lost += lost
+        return rows, lost
 
     # ------------------------------------------------------------------ held-out evaluation (DESIGN §9, f6)
     def eval_forward(self):
@@ -487,7 +569,9 @@ class TrainStepEngine:
     def _capture(self, exchange_in_graph: bool):
         # the warm-up launches below are real steps: snapshot the trainable / RNG state and put it back — ALSO when the
         # capture raises (the fallback re-captures from the same state, not from one optimizer step later)
-        saved = (self.params, self.exp_avg, self.exp_avg_sq, self.opt_step, self.scaler, self.rng_state, self.seg_step)
+        # (and the record's ring, its counter and the norm outputs: the warm-up must leave no rows behind)
+        saved = (self.params, self.exp_avg, self.exp_avg_sq, self.opt_step, self.scaler, self.rng_state, self.seg_step,
+                 *self._ephemeral)
         state = [t.clone() for t in saved]
         try:
             self._capture_graphs(exchange_in_graph)

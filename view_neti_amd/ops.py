@@ -354,6 +354,63 @@ def adamw_segments(p, g, m, v, seg_len, n_seg, seg_step, active, hyper, scaler, 
             _p(hyper), _p(scaler), _p(step), growth_interval, phases, stream())
 
 
+def adamw_flat_clipped(p, g, m, v, hyper, scaler, step, clip_coef, growth_interval=2000, phases=OPT_ALL):
+    """adamw_flat with the unscaled gradient multiplied by the device scalar clip_coef[0] (norm_out[NORM_CLIP_COEF:])"""
+    _l.call("adamw_flat_clipped", _p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), _p(scaler), _p(step), growth_interval,
+            phases, _p(clip_coef), stream())
+
+
+def adamw_segments_clipped(p, g, m, v, seg_len, n_seg, seg_step, active, hyper, scaler, step, clip_coef,
+                           growth_interval=2000, phases=OPT_ALL):
+    _l.call("adamw_segments_clipped", _p(p), _p(g), _p(m), _p(v), seg_len, n_seg, _p(seg_step), _p(active), active.numel(),
+            _p(hyper), _p(scaler), _p(step), growth_interval, phases, _p(clip_coef), stream())
+
+
+# vneti_grad_norm_finish's output (include/vneti.h)
+NORM_OBJECT, NORM_VIEW, NORM_TOTAL, NORM_FINITE, NORM_CLIP_COEF, NORM_OUT_FLOATS = 0, 1, 2, 3, 4, 5
+# a row of the telemetry ring (VNETI_TELEMETRY_*): header, then timesteps[B], losses[B]
+(TEL_SEQ, TEL_MICRO, TEL_CLOSED, TEL_NORM_OBJECT, TEL_NORM_VIEW, TEL_NORM_TOTAL, TEL_FINITE, TEL_CLIP_COEF, TEL_LOSS_SCALE,
+ TEL_LR, TEL_HEADER) = range(11)
+
+
+def telemetry_row_floats(Bn):
+    return TEL_HEADER + 2 * Bn
+
+
+def grad_sumsq_ws_doubles(length, n_active=0):
+    n = _l.query("grad_sumsq_ws_doubles", length, n_active)
+    if n < 0:
+        raise RuntimeError(f"grad_sumsq: unsupported shape len={length} n_active={n_active}")
+    return n
+
+
+def grad_sumsq(g, ws, seg_len=None, active=None):
+    """f64 partial sums of squares of the flat f32 range `g` (active None) or of its segments `active` (device int32 ids)
+    of seg_len floats, into ws (float64)"""
+    assert g.dtype == torch.float32 and ws.dtype == torch.float64 and g.is_contiguous()
+    length, n_active = (g.numel(), 0) if active is None else (seg_len, active.numel())
+    assert active is None or g.numel() % seg_len == 0
+    assert ws.numel() >= grad_sumsq_ws_doubles(length, n_active), "grad_sumsq: workspace too small"
+    _l.call("grad_sumsq", _p(g), length, _p(active), n_active, _p(ws), stream())
+
+
+def grad_norm_finish(ws_object, n_object, ws_view, n_view, scaler, hyper, max_norm, out, ring=None, count=None, rows=0,
+                     row_floats=0):
+    assert out.numel() >= NORM_OUT_FLOATS and (ws_object is None or ws_object.numel() >= n_object)
+    assert ws_view is None or ws_view.numel() >= n_view
+    assert ring is None or ring.numel() >= rows * row_floats
+    _l.call("grad_norm_finish", _p(ws_object) if n_object else None, n_object, _p(ws_view) if n_view else None, n_view,
+            _p(scaler), _p(hyper), _p(max_norm), _p(out), _p(ring), _p(count), rows, row_floats, stream())
+
+
+def train_record(ring, count, rows, first_micro, timesteps, losses, Bn):
+    """the micro-step's part of ring row count % rows (timesteps int64[Bn], losses f32[Bn]); advances count"""
+    assert timesteps.dtype == torch.int64 and timesteps.numel() >= Bn and losses.numel() >= Bn
+    W = telemetry_row_floats(Bn)
+    assert ring.dtype == torch.float32 and ring.numel() >= rows * W and count.dtype == torch.int32
+    _l.call("train_record", _p(ring), _p(count), rows, W, 1 if first_micro else 0, _p(timesteps), _p(losses), Bn, stream())
+
+
 def nested_dropout_mask(mask, nl, Bn, hidden, prob, state, stream_id):
     _l.call("nested_dropout_mask", _p(mask), nl, Bn, hidden, prob, _p(state), stream_id, stream())
 
