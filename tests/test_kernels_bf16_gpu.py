@@ -1,5 +1,6 @@
 """Per-kernel parity of the bf16 build: every case of the kernel files (tests/test_kernels_gpu.py, tests/test_text_kernels_gpu.py,
-tests/test_optim_rng_gpu.py, tests/test_kernel_contracts_gpu.py) against libvneti_hip_bf16.so.
+tests/test_optim_rng_gpu.py, tests/test_kernel_contracts_gpu.py, tests/test_autotune_variants_gpu.py) against
+libvneti_hip_bf16.so.
 
 A process computes in ONE 16-bit format (view_neti_amd/lib.py), so the bf16 run of the kernel file is a child pytest
 process with VNETI_PRECISION=bf16, one per GROUP of the file (so that a failure names its area and each child has a time
@@ -28,6 +29,7 @@ KERNEL_FILE = os.path.join("tests", "test_kernels_gpu.py")
 TEXT_FILE = os.path.join("tests", "test_text_kernels_gpu.py")
 OPTIM_RNG_FILE = os.path.join("tests", "test_optim_rng_gpu.py")
 CONTRACTS_FILE = os.path.join("tests", "test_kernel_contracts_gpu.py")
+VARIANTS_FILE = os.path.join("tests", "test_autotune_variants_gpu.py")
 
 # group -> (kernel file, `-k` expression, time limit of the child in seconds).  The limits are several times the wall times
 # measured on an MI355X (the tables of the per-kernel parity runs), and never above 300 s.
@@ -46,9 +48,13 @@ GROUPS = {
     "contracts_conv": (CONTRACTS_FILE, "contract_conv", 60),
     "contracts_norms": (CONTRACTS_FILE, "contract_norm", 60),
     "contracts_attention": (CONTRACTS_FILE, "contract_attn", 60),
+    # every autotuner variant of the engines' own GEMM launches (one child per engine family)
+    "variants_unet": (VARIANTS_FILE, "unet", 120),
+    "variants_vae": (VARIANTS_FILE, "vae", 60),
+    "variants_text": (VARIANTS_FILE, "text", 60),
 }
 # kernel file -> the least number of cases its collection must hold (a file that lost its tests cannot pass as "covered")
-KERNEL_FILES = {KERNEL_FILE: 500, TEXT_FILE: 120, OPTIM_RNG_FILE: 30, CONTRACTS_FILE: 100}
+KERNEL_FILES = {KERNEL_FILE: 500, TEXT_FILE: 120, OPTIM_RNG_FILE: 30, CONTRACTS_FILE: 100, VARIANTS_FILE: 11}
 DEATH_CODES = (124, 134, 137, 139)  # time limit, abort, kill, segmentation fault (a negative code is a signal)
 
 _dead = None        # "group X died with rc N": set once, read by every later group
