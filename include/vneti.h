@@ -300,6 +300,17 @@ int vneti_sample_add_noise(const void* moments, long long ldm, const float* eps,
                            const float* alphas_cumprod, float scaling, int v_prediction,
                            float* latents, float* noisy, float* target, int Bn, int Lc, int HW,
                            void* stream);
+/* vneti_sample_add_noise with offset noise (extension: optim.noise_offset).  Restates the
+ * `noise_offset` line of diffusers' examples/text_to_image/train_text_to_image.py,
+ *   noise += noise_offset * torch.randn((B, C, 1, 1)),
+ * from the published algorithm, PARITY UNPINNED against the package; the reference itself has no such option.
+ * offs: f32 [Bn][Lc], one N(0,1) draw per (sample, channel).  n' = fmaf(offset, offs[b*Lc + c], noise[gid]); noisy and
+ * target are formed from n' exactly as the entry above forms them from noise (for epsilon the target IS n').  The noise
+ * buffer is only read.  offset = 0 gives the entry above bit for bit. */
+int vneti_sample_add_noise_offset(const void* moments, long long ldm, const float* eps, const float* noise,
+                                  const void* timesteps_i64, const float* alphas_cumprod, float scaling,
+                                  int v_prediction, float* latents, float* noisy, float* target, int Bn, int Lc,
+                                  int HW, const float* offs, float offset, void* stream);
 /* The same three steps as separate entry points (identical arithmetic), for callers that keep the reference's
  * module-call order: `vae.encode(x).latent_dist.sample()` (training/coach.py:165-169; scaling = 1 leaves the
  * multiplication by vae.config.scaling_factor to the caller) ... */
@@ -358,6 +369,18 @@ int vneti_image_postprocess(const void* img, long long ldi, float* out, long lon
 int vneti_mse_loss_grad(const void* pred, long long ldp, const float* target, void* dpred,
                         long long lddp, float* loss_sum, const float* loss_scale, int Bn, int Lc,
                         int HW, void* stream);
+/* vneti_mse_loss_grad with Min-SNR-gamma weighting (extension: optim.snr_gamma; Hang et al. 2023).
+ * Restates `compute_snr` and the `snr_gamma` block of diffusers' examples/text_to_image/train_text_to_image.py from the
+ * published algorithm, PARITY UNPINNED against the package; the reference itself weights every timestep alike.  Per
+ * sample b, in f32, inside the same single launch:
+ *   a = alphas_cumprod[t[b]];  snr = a / (1 - a);  w_b = min(snr, gamma) / (v_prediction ? snr + 1 : snr)
+ *   loss_sum += sum w_b (pred - target)^2;   dpred = 2 (pred - target) w_b / N * loss_scale[0],   N = Bn Lc HW
+ * so loss_sum / N is mean_b(w_b * mean_chw(d^2)), diffusers' weighted loss.  gamma > 0; +inf is legal: for epsilon it
+ * makes every w_b exactly 1 and the launch bit-identical to vneti_mse_loss_grad. */
+int vneti_mse_loss_grad_snr(const void* pred, long long ldp, const float* target, void* dpred, long long lddp,
+                            float* loss_sum, const float* loss_scale, int Bn, int Lc, int HW,
+                            const void* timesteps_i64, const float* alphas_cumprod, float gamma, int v_prediction,
+                            void* stream);
 /* F.mse_loss(pred.float(), target.float(), reduction="none").mean(dim=(1,2,3)): one loss per sample, forward only.  The
  * held-out evaluation of a run (view_neti_amd/compat/heldout.py): the batch-mean form of training/coach.py:211 split by
  * sample, so that a loss can be attributed to a camera the way training/validate.py:65-186 attributes its image metrics.

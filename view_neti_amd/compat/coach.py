@@ -129,6 +129,8 @@ class Coach:
             nested_dropout_prob=m.nested_dropout_prob if m.use_nested_dropout else 0.0,
             moment_cache_images=0 if forward_only else self._moment_cache_size(), need_backward=not forward_only,
             max_grad_norm=None if forward_only else cfg.optim.max_grad_norm,
+            snr_gamma=None if forward_only else cfg.optim.snr_gamma,
+            noise_offset=None if forward_only else cfg.optim.noise_offset,
             telemetry_rows=self._telemetry_rows(), **first.engine_encoder_kwargs(), **kw)
         # per-step record (extension): every rank records (one launch list for all), rank 0 writes the file
         self.metrics = None
@@ -231,7 +233,8 @@ class Coach:
         cfg = self.cfg
         return resume.fingerprint(cfg.learnable_mode, cfg.optim.train_batch_size, cfg.optim.gradient_accumulation_steps,
                                   self.world, cfg.optim.mixed_precision, cfg.seed, len(self.train_dataset), n_params,
-                                  max_grad_norm=cfg.optim.max_grad_norm)
+                                  max_grad_norm=cfg.optim.max_grad_norm, snr_gamma=cfg.optim.snr_gamma,
+                                  noise_offset=cfg.optim.noise_offset)
 
     def _telemetry_rows(self) -> int:
         """the ring holds twice the micro-steps between two reads (the loop reads it at every 50th optimizer step)"""
@@ -252,7 +255,13 @@ class Coach:
         if lost or dropped:
             self.log(f"WARNING: train metrics: {lost} micro-step(s) overwritten in the ring before they were read, "
                      f"{dropped} more dropped with their group")
-        self.metrics.append(lines_up_to(groups, global_step, omit_object=self.mapper_object_lookup is None))
+        snr = {}
+        if self.engine.snr_gamma is not None:  # "loss_weighted" beside the unweighted "loss" 
+            if not hasattr(self, "_ac_host"):
+                self._ac_host = self.engine.ac.cpu().numpy()
+            snr = dict(snr_gamma=self.engine.snr_gamma, alphas_cumprod=self._ac_host,
+                       v_prediction=self.engine.cfg.ddpm.prediction_type == "v_prediction")
+        self.metrics.append(lines_up_to(groups, global_step, omit_object=self.mapper_object_lookup is None, **snr))
 
     def _load_resume_mappers(self, directory=None, step: Optional[int] = None):
         """the mappers this run TRAINS take their weights from the checkpoint pair (a frozen view mapper, modes 4 / 5,

@@ -222,10 +222,19 @@ class OptimConfig:
     # checkpoint's cfg and enters the resume fingerprint — where it is set ("when_set": config.yaml and a checkpoint's
     # extension fields of a run without it are the ones they always were)
     max_grad_norm: Optional[float] = field(default=None, metadata={"ext": True, "when_set": True})
+    # extensions, the two objective controls of diffusers' trainers, under the same rules as max_grad_norm:
+    # snr_gamma — Min-SNR-gamma loss weighting (--snr_gamma; `inf` weights every timestep alike); noise_offset — offset
+    # noise, noise += noise_offset * randn(B, C, 1, 1) (--noise_offset).  Held-out losses stay unweighted and offset-free.
+    snr_gamma: Optional[float] = field(default=None, metadata={"ext": True, "when_set": True})
+    noise_offset: Optional[float] = field(default=None, metadata={"ext": True, "when_set": True})
 
     def __post_init__(self):
-        if self.max_grad_norm is not None and not self.max_grad_norm > 0:
-            raise ValueError(f"optim.max_grad_norm must be > 0 when set (is {self.max_grad_norm})")
+        for name in ("max_grad_norm", "snr_gamma", "noise_offset"):
+            v = getattr(self, name)
+            if v is not None and not v > 0:
+                raise ValueError(f"optim.{name} must be > 0 when set (is {v})")
+        if self.noise_offset is not None and self.noise_offset == float("inf"):
+            raise ValueError("optim.noise_offset must be finite")
 
 
 @dataclass

@@ -235,7 +235,8 @@ def prune_states(directory, keep: int) -> List[Path]:
 
 # ---------------------------------------------------------------------------------------------- fingerprint
 def fingerprint(learnable_mode: int, batch_size: int, grad_accum: int, world: int, precision: str, seed: Optional[int],
-                dataset_len: int, n_params: Optional[int] = None, max_grad_norm: Optional[float] = None) -> Dict[str, Any]:
+                dataset_len: int, n_params: Optional[int] = None, max_grad_norm: Optional[float] = None,
+                snr_gamma: Optional[float] = None, noise_offset: Optional[float] = None) -> Dict[str, Any]:
     fp = {"learnable_mode": int(learnable_mode), "train_batch_size": int(batch_size),
           "gradient_accumulation_steps": int(grad_accum), "world_size": int(world), "precision": str(precision),
           "seed": -1 if seed is None else int(seed), "dataset_len": int(dataset_len)}
@@ -243,11 +244,15 @@ def fingerprint(learnable_mode: int, batch_size: int, grad_accum: int, world: in
         fp["n_params"] = int(n_params)
     if max_grad_norm is not None:  # only when set: the fingerprint of an unclipped run is the one it always was
         fp["max_grad_norm"] = float(max_grad_norm)
+    if snr_gamma is not None:  # (the same rule for the objective's options)
+        fp["snr_gamma"] = float(snr_gamma)
+    if noise_offset is not None:
+        fp["noise_offset"] = float(noise_offset)
     return fp
 
 
 # fields that are present only where they are set: absent on one side and present on the other is a difference too
-_WHEN_SET = ("max_grad_norm",)
+_WHEN_SET = ("max_grad_norm", "snr_gamma", "noise_offset")
 
 
 def check_fingerprint(saved: Dict[str, Any], current: Dict[str, Any]):

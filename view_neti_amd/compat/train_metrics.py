@@ -11,13 +11,16 @@ fetches the ring where the train loop already syncs; this module turns the rows 
 `loss` is the mean of the group's per-sample losses: the reference's `total_loss` averaged over the accumulation group.
 `samples` has one entry per sample of every micro-step of the group — the loss-by-timestep curve is read off these.  A side
 of `grad_norm` that the run does not train is omitted (mode 1: no object mapper; mode 5: a frozen view mapper); a non-finite
-norm (a skipped step) is null.  Pure functions and a small file writer: no GPU."""
+norm (a skipped step) is null.  A run with `optim.snr_gamma` (§9 f8) has one more key, `"loss_weighted"`: the Min-SNR
+weighted mean of the same samples — the quantity the step minimises — computed here in f64 from the (t, loss) pairs and the
+f32 `alphas_cumprod` table; `loss` stays the unweighted mean, so files of weighted and unweighted runs compare.  Pure
+functions and a small file writer: no GPU."""
 from __future__ import annotations
 
 import json
 import os
 from pathlib import Path
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 from ..engine.telemetry import finite_or_none
 
@@ -45,23 +48,40 @@ def group_rows(rows: List[Dict]) -> Tuple[List[List[Dict]], List[Dict], int]:
     return groups, cur, dropped
 
 
-def step_line(step: int, group: List[Dict], omit_object: bool = False, omit_view: bool = False) -> Dict:
-    """one optimizer step's line from the rows of its accumulation group (the last row closed it)"""
+def min_snr_weight(alpha_cumprod: float, gamma: float, v_prediction: bool = False) -> float:
+    """Min-SNR-gamma weight of one timestep in f64: snr = a / (1 - a); min(snr, gamma) / snr, or / (snr + 1) for
+    v-prediction (the formula of vneti_mse_loss_grad_snr, include/vneti.h)"""
+    a = float(alpha_cumprod)
+    snr = a / (1.0 - a)
+    return min(snr, float(gamma)) / (snr + 1.0 if v_prediction else snr)
+
+
+def step_line(step: int, group: List[Dict], omit_object: bool = False, omit_view: bool = False,
+              snr_gamma: Optional[float] = None, alphas_cumprod: Optional[Sequence[float]] = None,
+              v_prediction: bool = False) -> Dict:
+    """one optimizer step's line from the rows of its accumulation group (the last row closed it).  snr_gamma set: the
+    line gains "loss_weighted" (alphas_cumprod: the f32 table, indexable by timestep)"""
     last = group[-1]
     assert last["closed"], "the group's last micro-step did not close it"
     samples = [{"t": t, "loss": l} for r in group for t, l in zip(r["timesteps"], r["losses"])]
     norm = {k: finite_or_none(v) for k, v in last["grad_norm"].items()
             if not (k == "object" and omit_object) and not (k == "view" and omit_view)}
     norm = {k: norm[k] for k in ("object", "view", "total") if k in norm}
-    return {"step": int(step), "loss": finite_or_none(sum(s["loss"] for s in samples) / len(samples)), "lr": last["lr"],
+    line = {"step": int(step), "loss": finite_or_none(sum(s["loss"] for s in samples) / len(samples)), "lr": last["lr"],
             "loss_scale": last["loss_scale"], "skipped": bool(last["skipped"]), "grad_norm": norm,
             "clip_coef": last["clip_coef"], "samples": [{"t": s["t"], "loss": finite_or_none(s["loss"])} for s in samples]}
+    if snr_gamma is not None:
+        if alphas_cumprod is None:
+            raise ValueError("step_line(): snr_gamma needs the alphas_cumprod table")
+        w = [min_snr_weight(alphas_cumprod[int(s["t"])], snr_gamma, v_prediction) for s in samples]
+        line["loss_weighted"] = finite_or_none(sum(wi * float(s["loss"]) for wi, s in zip(w, samples)) / len(samples))
+    return line
 
 
-def lines_up_to(groups: List[List[Dict]], step: int, **omit) -> List[Dict]:
-    """the groups are the LAST len(groups) optimizer steps up to and including `step`"""
+def lines_up_to(groups: List[List[Dict]], step: int, **kw) -> List[Dict]:
+    """the groups are the LAST len(groups) optimizer steps up to and including `step`; kw: step_line's options"""
     first = step - len(groups) + 1
-    return [step_line(first + i, g, **omit) for i, g in enumerate(groups)]
+    return [step_line(first + i, g, **kw) for i, g in enumerate(groups)]
 
 
 def truncate_file(path, step: int) -> int:

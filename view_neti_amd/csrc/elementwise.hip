@@ -205,10 +205,14 @@ __device__ __forceinline__ void vn_add_noise(float z, float n, float a, int vpre
   target = vpred ? fmaf(sa, n, -(sb * z)) : n;
 }
 
+// OFFSET (the _offset entry): the noise is n' = noise + offset * offs[b][c], one draw per (sample, channel) broadcast over
+// the pixels (diffusers' noise_offset); noisy and target are formed from n', the noise buffer is only read.  offset = 0
+// changes no bit.  OFFSET = false is the body the plain entry always had: offs and offset are never read.
+template <bool OFFSET>
 __global__ void sample_add_noise_kernel(const half_t* moments, long long ldm, const float* eps,
                                         const float* noise, const long long* t, const float* ac, float scaling,
                                         int vpred, float* latents, float* noisy, float* target, int Bn, int Lc,
-                                        int HW) {
+                                        int HW, const float* offs, float offset) {
   int gid = blockIdx.x * blockDim.x + threadIdx.x;
   int total = Bn * Lc * HW;
   if (gid >= total) return;
@@ -216,8 +220,10 @@ __global__ void sample_add_noise_kernel(const half_t* moments, long long ldm, co
   int c = (gid / HW) % Lc;
   int b = gid / (HW * Lc);
   float z = vn_latent_sample(moments + ((long long)b * HW + p) * ldm, c, Lc, eps[gid], scaling);
+  float n = noise[gid];
+  if constexpr (OFFSET) n = fmaf(offset, offs[b * Lc + c], n);
   float ny, tg;
-  vn_add_noise(z, noise[gid], ac[t[b]], vpred, ny, tg);
+  vn_add_noise(z, n, ac[t[b]], vpred, ny, tg);
   latents[gid] = z;
   noisy[gid] = ny;
   target[gid] = tg;
@@ -408,9 +414,16 @@ __global__ void image_postprocess_kernel(const half_t* img, long long ldi, float
 // ---- MSE loss + gradient seed -------------------------------------------------------------------
 // pred: NHWC f16 [B*HW][ldp] (Lc channels used); target NCHW f32.  loss_sum += sum (p-t)^2 (one
 // atomic per block); dpred (NHWC f16) = 2*(p-t)/N * loss_scale[0].
+// SNR (the _snr entry): sample b's terms are multiplied by the Min-SNR-gamma weight w_b of its timestep (diffusers
+// compute_snr: snr = ac/(1-ac); w = min(snr, gamma)/snr, or /(snr+1) for v-prediction), computed here in f32 —
+// always, also when w is 1 (then it changes no bit).  SNR = false is the body the unweighted entry always had: t, ac,
+// gamma and vpred are never read.
+template <bool SNR>
 __global__ __launch_bounds__(256) void mse_loss_grad_kernel(const half_t* pred, long long ldp, const float* target,
                                                             half_t* dpred, long long lddp, float* loss_sum,
-                                                            const float* loss_scale, int Bn, int Lc, int HW) {
+                                                            const float* loss_scale, int Bn, int Lc, int HW,
+                                                            const long long* t, const float* ac, float gamma,
+                                                            int vpred) {
   __shared__ float red[4];
   int gid = blockIdx.x * 256 + threadIdx.x;
   int total = Bn * Lc * HW;
@@ -422,8 +435,16 @@ __global__ __launch_bounds__(256) void mse_loss_grad_kernel(const half_t* pred, 
     float pv = (float)pred[((long long)b * HW + p) * ldp + c];
     float tv = target[((long long)b * Lc + c) * HW + p];
     float d = pv - tv;
-    sq = d * d;
-    dpred[((long long)b * HW + p) * lddp + c] = (half_t)(2.f * d / (float)total * loss_scale[0]);
+    if constexpr (SNR) {
+      float a = ac[t[b]];
+      float snr = a / (1.f - a);
+      float w = fminf(snr, gamma) / (vpred ? snr + 1.f : snr);
+      sq = d * d * w;
+      dpred[((long long)b * HW + p) * lddp + c] = (half_t)(2.f * d * w / (float)total * loss_scale[0]);
+    } else {
+      sq = d * d;
+      dpred[((long long)b * HW + p) * lddp + c] = (half_t)(2.f * d / (float)total * loss_scale[0]);
+    }
   }
   sq = wave_sum(sq);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
@@ -788,10 +809,25 @@ extern "C" int vneti_sample_add_noise(const void* moments, long long ldm, const 
   VN_REQUIRE(moments && eps && noise && timesteps && alphas_cumprod && latents && noisy && target,
              "sample_add_noise: null pointer");
   int n = Bn * Lc * HW;
-  hipLaunchKernelGGL(sample_add_noise_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ST, (const half_t*)moments, ldm,
+  hipLaunchKernelGGL(sample_add_noise_kernel<false>, dim3(cdiv(n, 256)), dim3(256), 0, ST, (const half_t*)moments, ldm,
                      eps, noise, (const long long*)timesteps, alphas_cumprod, scaling, v_prediction, latents, noisy,
-                     target, Bn, Lc, HW);
+                     target, Bn, Lc, HW, (const float*)nullptr, 0.f);
   return vneti_check_launch("sample_add_noise");
+}
+
+extern "C" int vneti_sample_add_noise_offset(const void* moments, long long ldm, const float* eps, const float* noise,
+                                             const void* timesteps, const float* alphas_cumprod, float scaling,
+                                             int v_prediction, float* latents, float* noisy, float* target, int Bn,
+                                             int Lc, int HW, const float* offs, float offset, void* stream) {
+  VN_REQUIRE(moments && eps && noise && timesteps && alphas_cumprod && latents && noisy && target && offs,
+             "sample_add_noise_offset: null pointer");
+  VN_REQUIRE(Bn > 0 && Lc > 0 && HW > 0 && ldm >= 2LL * Lc && (long long)Bn * Lc * HW < 0x7fffffffLL,
+             "sample_add_noise_offset: bad shape Bn=%d Lc=%d HW=%d ldm=%lld", Bn, Lc, HW, ldm);
+  int n = Bn * Lc * HW;
+  hipLaunchKernelGGL(sample_add_noise_kernel<true>, dim3(cdiv(n, 256)), dim3(256), 0, ST, (const half_t*)moments, ldm,
+                     eps, noise, (const long long*)timesteps, alphas_cumprod, scaling, v_prediction, latents, noisy,
+                     target, Bn, Lc, HW, offs, offset);
+  return vneti_check_launch("sample_add_noise_offset");
 }
 
 extern "C" int vneti_latent_sample(const void* moments, long long ldm, const float* eps, float scaling, float* latents,
@@ -914,9 +950,26 @@ extern "C" int vneti_mse_loss_grad(const void* pred, long long ldp, const float*
                                    int HW, void* stream) {
   VN_REQUIRE(pred && target && dpred && loss_sum && loss_scale, "mse_loss_grad: null pointer");
   int n = Bn * Lc * HW;
-  hipLaunchKernelGGL(mse_loss_grad_kernel, dim3(cdiv(n, 256)), dim3(256), 0, ST, (const half_t*)pred, ldp, target,
-                     (half_t*)dpred, lddp, loss_sum, loss_scale, Bn, Lc, HW);
+  hipLaunchKernelGGL(mse_loss_grad_kernel<false>, dim3(cdiv(n, 256)), dim3(256), 0, ST, (const half_t*)pred, ldp, target,
+                     (half_t*)dpred, lddp, loss_sum, loss_scale, Bn, Lc, HW, (const long long*)nullptr,
+                     (const float*)nullptr, 0.f, 0);
   return vneti_check_launch("mse_loss_grad");
+}
+
+extern "C" int vneti_mse_loss_grad_snr(const void* pred, long long ldp, const float* target, void* dpred,
+                                       long long lddp, float* loss_sum, const float* loss_scale, int Bn, int Lc,
+                                       int HW, const void* timesteps, const float* alphas_cumprod, float gamma,
+                                       int v_prediction, void* stream) {
+  VN_REQUIRE(pred && target && dpred && loss_sum && loss_scale && timesteps && alphas_cumprod,
+             "mse_loss_grad_snr: null pointer");
+  VN_REQUIRE(Bn > 0 && Lc > 0 && HW > 0 && ldp >= Lc && lddp >= Lc && (long long)Bn * Lc * HW < 0x7fffffffLL,
+             "mse_loss_grad_snr: bad shape Bn=%d Lc=%d HW=%d ldp=%lld lddp=%lld", Bn, Lc, HW, ldp, lddp);
+  VN_REQUIRE(gamma > 0.f, "mse_loss_grad_snr: gamma must be > 0 (+inf: every weight is 1)");
+  int n = Bn * Lc * HW;
+  hipLaunchKernelGGL(mse_loss_grad_kernel<true>, dim3(cdiv(n, 256)), dim3(256), 0, ST, (const half_t*)pred, ldp, target,
+                     (half_t*)dpred, lddp, loss_sum, loss_scale, Bn, Lc, HW, (const long long*)timesteps,
+                     alphas_cumprod, gamma, v_prediction);
+  return vneti_check_launch("mse_loss_grad_snr");
 }
 
 extern "C" long long vneti_mse_loss_per_sample_ws_floats(int Bn, int HW) {

@@ -53,14 +53,19 @@ class TrainStepEngine:
                  nested_dropout_prob: float = 0.0, hidden_object: int = 64,
                  legacy_pe_object: Optional[torch.Tensor] = None, enc_dim_object: int = 64,
                  output_bypass_object: bool = True, output_bypass_view: bool = True, exchange=None,
-                 moment_cache_images: int = 0, max_grad_norm: Optional[float] = None, telemetry_rows: int = 0):
+                 moment_cache_images: int = 0, max_grad_norm: Optional[float] = None, telemetry_rows: int = 0,
+                 snr_gamma: Optional[float] = None, noise_offset: Optional[float] = None):
         """mapper_object: one mapper state_dict, or a list of them (learnable_mode 3: one object mapper per
         scene, `mapper_object_lookup`, training/coach.py:505-552) — `set_batch(object_index=k)` picks the one
         the batch trains.
         max_grad_norm: clip the (unscaled, mean) mapper gradient to this global L2 norm before AdamW, as
         torch.nn.utils.clip_grad_norm_ after GradScaler.unscale_ would.  telemetry_rows: > 0 keeps a device ring of that
         many micro-steps (timesteps, per-sample losses, gradient norms, loss scale, lr, skipped steps) for
-        read_telemetry().  Both off: the step enqueues the launches it always did."""
+        read_telemetry().  Both off: the step enqueues the launches it always did.
+        snr_gamma: Min-SNR-gamma weighting of the training loss (diffusers' --snr_gamma; inf is legal: every weight 1).
+        noise_offset: offset noise, noise += noise_offset * randn(B, C, 1, 1) (diffusers' --noise_offset).  Both are None
+        or > 0 and touch the TRAINING objective only: eval_losses() stays the plain MSE on plain noise, and the ring's
+        per-sample losses stay unweighted.  Both off: the step enqueues the launches it always did."""
         from .text import flatten_mapper_state
         self.cfg = cfg
         self.B, self.H, self.W = batch, height, width
@@ -227,6 +232,18 @@ class TrainStepEngine:
             self._tele_read = 0       # the counter at the last read_telemetry()
             self.telemetry_lost = 0   # micro-steps overwritten before they were read, over the engine's life
             self._ephemeral += (self.tele_buf,)
+        # ---- the training objective's options.  Neither is trainer state: the offset draw is stream 5 of
+        # rng_state.  (`not x > 0` also refuses nan)
+        if snr_gamma is not None and not float(snr_gamma) > 0.0:
+            raise ValueError(f"snr_gamma must be > 0, inf allowed (is {snr_gamma!r}); None turns the weighting off")
+        if noise_offset is not None and not 0.0 < float(noise_offset) < float("inf"):
+            raise ValueError(f"noise_offset must be > 0 and finite (is {noise_offset!r}); None turns offset noise off")
+        self.snr_gamma = None if snr_gamma is None else float(snr_gamma)
+        self.noise_offset = None if noise_offset is None else float(noise_offset)
+        self.offset_noise = None  # f32 [B][Lc]: one draw per (sample, channel), allocated before any capture
+        if self.noise_offset is not None:
+            self.offset_noise = torch.zeros(batch, Lc, dtype=torch.float32, device=device)
+            self._offset_noise_set = False  # host-supplied randomness: has set_noise() delivered the draw
 
     # ------------------------------------------------------------------ inputs
     def set_batch(self, pixel_values, input_ids, placeholder_object, placeholder_view=None, view_params=None,
@@ -277,8 +294,21 @@ class TrainStepEngine:
     def view_params_flat(self) -> torch.Tensor:
         return self.params[self.n_all_obj:]
 
-    def set_noise(self, eps, noise, timesteps):
-        """host-supplied randomness (parity tests: identical values for the oracle and the GPU)."""
+    def set_noise(self, eps, noise, timesteps, offset_noise=None):
+        """host-supplied randomness (parity tests: identical values for the oracle and the GPU).  offset_noise: the (B, Lc)
+        draw of offset noise: required by an engine built with noise_offset and without the device RNG (with it, stream 5
+        draws it in the step, and the held-out evaluation, which calls this, never reads it); refused by an engine without
+        noise_offset."""
+        if offset_noise is None and self.noise_offset is not None and not self.device_rng:
+            raise ValueError("set_noise(): an engine with noise_offset and device_rng=False needs the (B, Lc) offset_noise draw")
+        if offset_noise is not None and self.noise_offset is None:
+            raise ValueError("set_noise(): offset_noise given, but this engine has no noise_offset")
+        if offset_noise is not None:
+            if tuple(offset_noise.shape) != tuple(self.offset_noise.shape):
+                raise ValueError(f"set_noise(): offset_noise has shape {tuple(offset_noise.shape)}, expected "
+                                 f"{tuple(self.offset_noise.shape)}")
+            self.offset_noise.copy_(offset_noise)
+            self._offset_noise_set = True
         self.eps.copy_(eps)
         self.noise.copy_(noise)
         self.timesteps.copy_(timesteps)
@@ -292,12 +322,14 @@ class TrainStepEngine:
     # ------------------------------------------------------------------ trainer state (resumable training)
     _STATE = ("params", "exp_avg", "exp_avg_sq", "opt_step", "seg_step", "scaler", "rng_state", "hyper")
 
+    _WHEN_SET = ("max_grad_norm", "snr_gamma", "noise_offset")  # described only where set: older states read as "unset"
+
     def _describe(self) -> Dict:
         from .. import lib
         return {"n_params": self.params.numel(), "n_objects": self.n_objects, "n_obj": self.n_obj,
                 "view_in_bucket": self.params.numel() > self.n_all_obj, "grad_accum": self.grad_accum,
                 "world_size": self.world_size, "precision": lib.precision(),
-                **({"max_grad_norm": self.max_grad_norm} if self.max_grad_norm is not None else {})}
+                **{k: getattr(self, k) for k in self._WHEN_SET if getattr(self, k) is not None}}
 
     def state_dict(self) -> Dict:
         """CPU copies of everything the captured step reads and writes in place — the set `_capture` snapshots around its
@@ -319,8 +351,8 @@ class TrainStepEngine:
             raise RuntimeError("load_state_dict() inside a gradient-accumulation group")
         want, have = self._describe(), sd.get("meta", {})
         bad = [f"{k}: saved {have.get(k)!r}, this engine {v!r}" for k, v in want.items() if have.get(k) != v]
-        if "max_grad_norm" in have and "max_grad_norm" not in want:  # (a state from before f7 has no such key: unclipped)
-            bad.append(f"max_grad_norm: saved {have['max_grad_norm']!r}, this engine None")
+        # (a state from before f7 / f8 has no such keys: unclipped, unweighted, no offset noise)
+        bad += [f"{k}: saved {have[k]!r}, this engine None" for k in self._WHEN_SET if k in have and k not in want]
         bad += [f"{name}: saved shape {tuple(sd[name].shape) if name in sd else None}, this engine "
                 f"{tuple(getattr(self, name).shape)}" for name in self._STATE
                 if name not in sd or sd[name].shape != getattr(self, name).shape or sd[name].dtype != getattr(self, name).dtype]
@@ -341,9 +373,17 @@ class TrainStepEngine:
             ops.rng_fill_randint(self.timesteps, self.cfg.ddpm.num_train_timesteps, self.rng_state, 0)
             ops.rng_fill_normal(self.eps, self.rng_state, 1)
             ops.rng_fill_normal(self.noise, self.rng_state, 2)
-        self._forward_half(cached, bool(self.n_cache), fork=self.overlap)
+            if self.noise_offset is not None:  # (streams 3 and 4 are the nested-dropout masks of the two mappers)
+                ops.rng_fill_normal(self.offset_noise, self.rng_state, 5)
+        elif self.noise_offset is not None and not self._offset_noise_set:
+            raise RuntimeError("noise_offset without the device RNG: set_noise(..., offset_noise=) has to deliver the draw")
+        self._forward_half(cached, bool(self.n_cache), fork=self.overlap, noise_offset=self.noise_offset)
         self.loss_sum.zero_()
-        ops.mse_loss_grad(self.unet.pred, self.target, self.unet.dpred, self.loss_sum, self.scaler, B, Lc, hw)
+        if self.snr_gamma is None:
+            ops.mse_loss_grad(self.unet.pred, self.target, self.unet.dpred, self.loss_sum, self.scaler, B, Lc, hw)
+        else:
+            ops.mse_loss_grad_snr(self.unet.pred, self.target, self.unet.dpred, self.loss_sum, self.scaler, B, Lc, hw,
+                                  self.timesteps, self.ac, self.snr_gamma, self.cfg.ddpm.prediction_type == "v_prediction")
         if self.telemetry_rows:  # the micro-step's row: timesteps + the deterministic per-sample losses, then count += 1
             ops.mse_loss_per_sample(self.unet.pred, self.target, self.rec_loss, self.rec_ws, B, Lc, hw)
             ops.train_record(self.tele_ring, self.tele_count, self.telemetry_rows, not accumulate, self.timesteps,
@@ -352,10 +392,11 @@ class TrainStepEngine:
             self.unet.backward()
             self.text.backward()
 
-    def _forward_half(self, cached: bool, write_cache: bool, fork: bool = False):
+    def _forward_half(self, cached: bool, write_cache: bool, fork: bool = False, noise_offset: Optional[float] = None):
         """VAE moments -> sample_add_noise -> text pass -> UNet forward, shared by the train step and the held-out
         evaluation.  cached: the moments come out of the moment cache (no encoder launches); write_cache: the encoder's
-        moments are stored at the batch's image slots."""
+        moments are stored at the batch's image slots.  noise_offset: the train step passes its option; the evaluation
+        passes none whatever the engine was built with, so its launches and its numbers do not depend on the objective."""
         B, Lc, hw = self.B, self.cfg.vae.latent_channels, self.h * self.w
         # fork (overlap=True): the 16 mapper+CLIP passes (many small launches) run beside the VAE encoder (few large ones) on
         # a second stream; each schedule owns its split-K scratch, so they never alias.  OFF by default since round 6: both
@@ -374,9 +415,12 @@ class TrainStepEngine:
             self.vae.forward()
             if write_cache:
                 self.mcache.index_copy_(0, self.img_idx, self.vae.moments.view(B, hw, 2 * Lc))
-        ops.sample_add_noise(self.vae.moments, self.eps, self.noise, self.timesteps, self.ac,
-                             self.cfg.vae.scaling_factor, self.cfg.ddpm.prediction_type == "v_prediction", self.latents,
-                             self.unet.x_in, self.target, B, Lc, hw)
+        noise_args = (self.vae.moments, self.eps, self.noise, self.timesteps, self.ac, self.cfg.vae.scaling_factor,
+                      self.cfg.ddpm.prediction_type == "v_prediction", self.latents, self.unet.x_in, self.target, B, Lc, hw)
+        if noise_offset is None:
+            ops.sample_add_noise(*noise_args)
+        else:
+            ops.sample_add_noise_offset(*noise_args, self.offset_noise, noise_offset)
         if fork:
             main.wait_stream(self.side)  # join
         else:
@@ -643,7 +687,8 @@ class TrainStepEngine:
         return True
 
     def loss(self) -> float:
-        """mean squared error of the last step (forces a device sync — call sparingly)."""
+        """the training loss of the last step: the mean squared error, Min-SNR weighted when snr_gamma is set — the quantity
+        being minimised (forces a device sync — call sparingly)."""
         return float(self.loss_sum.item()) / self.n_loss
 
     # ------------------------------------------------------------------ introspection

@@ -258,6 +258,13 @@ def sample_add_noise(moments, eps, noise, t, ac, scaling, vpred, latents, noisy,
             1 if vpred else 0, _p(latents), _p(noisy), _p(target), Bn, Lc, HW, stream())
 
 
+def sample_add_noise_offset(moments, eps, noise, t, ac, scaling, vpred, latents, noisy, target, Bn, Lc, HW, offs, offset):
+    """sample_add_noise on the noise n' = noise + offset * offs[b][c] (offs: f32 [Bn][Lc]); `noise` itself is only read"""
+    assert offs.dtype == torch.float32 and offs.is_contiguous() and offs.numel() >= Bn * Lc
+    _l.call("sample_add_noise_offset", _p(moments), _ld(moments), _p(eps), _p(noise), _p(t), _p(ac), scaling,
+            1 if vpred else 0, _p(latents), _p(noisy), _p(target), Bn, Lc, HW, _p(offs), float(offset), stream())
+
+
 def gn_sums_decode(sums: torch.Tensor) -> torch.Tensor:
     """[..., 4] int64 slot sums (S1.hi, S1.lo, S2.hi, S2.lo: the fixed-point accumulators of csrc/common.h) -> [..., 2]
     float64 (sum, sum of squares); slots are summed by the caller as integers first (`.sum(dim)` on the int64 tensor)."""
@@ -324,6 +331,13 @@ def image_postprocess(img, out, n_pix, channels):
 def mse_loss_grad(pred, target, dpred, loss_sum, loss_scale, Bn, Lc, HW):
     _l.call("mse_loss_grad", _p(pred), _ld(pred), _p(target), _p(dpred), _ld(dpred), _p(loss_sum), _p(loss_scale),
             Bn, Lc, HW, stream())
+
+
+def mse_loss_grad_snr(pred, target, dpred, loss_sum, loss_scale, Bn, Lc, HW, t, ac, gamma, vpred):
+    """mse_loss_grad with sample b's terms weighted by min(snr, gamma) / (snr [+ 1 for v-prediction]), snr of ac[t[b]]"""
+    assert t.dtype == torch.int64 and t.numel() >= Bn and ac.dtype == torch.float32
+    _l.call("mse_loss_grad_snr", _p(pred), _ld(pred), _p(target), _p(dpred), _ld(dpred), _p(loss_sum), _p(loss_scale),
+            Bn, Lc, HW, _p(t), _p(ac), float(gamma), 1 if vpred else 0, stream())
 
 
 def mse_loss_per_sample_ws_floats(Bn, HW):
