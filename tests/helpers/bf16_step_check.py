@@ -17,13 +17,13 @@ assert lib.precision() == "bf16", "start this script with VNETI_PRECISION=bf16"
 name = sys.argv[1] if len(sys.argv) > 1 else "tiny"
 B, H, W = (int(v) for v in sys.argv[2:5]) if len(sys.argv) > 4 else (2, 64, 64)
 from oracle import sd_ref as R  # noqa: E402
-from test_step_gpu import build  # noqa: E402
+from helpers.engines import build_train_engine as build  # noqa: E402
 from view_neti_amd import synth  # noqa: E402
 from view_neti_amd.engine.text import flatten_mapper_state  # noqa: E402
 
 with_view = name != "sd15"
 torch.set_num_threads(min(32, len(os.sched_getaffinity(0))))
-cfg, eng, (uw, vw, cw), sd, w_enc, extra = build(name, B, H, W, with_view, device_rng=False, lr=4e-3)
+cfg, eng, (uw, vw, cw), sd, w_enc, extra = build(name, B, H, W, with_view=with_view, device_rng=False, lr=4e-3)
 assert eng.unet.pred.dtype == torch.bfloat16 and float(eng.scaler[0]) == 1.0  # bf16 buffers, no loss scaling (accelerate)
 ph, phv = cfg.clip.vocab_size - 3, cfg.clip.vocab_size - 4
 ids = synth.input_ids(B, ph, cfg.clip.vocab_size, view_placeholder_id=phv if with_view else None)

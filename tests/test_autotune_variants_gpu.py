@@ -29,18 +29,14 @@ and the variant that came closest to its bar per output kind.  Comparisons run o
 to describe a failure (and the few dozen GroupNorm words, which `ops.gn_sums_decode` decodes on the host).
 
 A status error of the library (RuntimeError) on a reachable variant fails the case at once."""
-import os
-import sys
 import time
 from functools import partial
 
 import pytest
 import torch
 
-from test_kernels_gpu import DEV, DT, ELEM_K, t16  # the kernel file's bars (tests/ is on sys.path: rootdir imports)
-
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
-import gemm_ref as G  # noqa: E402
+from helpers import gemm_ref as G
+from helpers.checks import DEV, DT, ELEM_K, t16  # the kernel files' bars
 
 pytestmark = pytest.mark.gpu
 

@@ -1,16 +1,13 @@
 """Host algebra of stochastic DDIM (eta > 0), no GPU: `ddim_eta_coefficients` (the six scalars the HIP step kernel reads)
 against the float64 restatement of DDIMScheduler.step in tests/helpers/ddim_eta_ref.py, and its eta = 0 row against
 `step_coefficients("ddim", ...)`."""
-import os
-import sys
 
 import pytest
 import torch
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
-import ddim_eta_ref as R  # noqa: E402
+from helpers import ddim_eta_ref as R
 
-from view_neti_amd.engine.infer import check_eta, ddim_eta_coefficients, inference_timesteps, step_coefficients  # noqa: E402
+from view_neti_amd.engine.infer import check_eta, ddim_eta_coefficients, inference_timesteps, step_coefficients
 
 
 @pytest.mark.parametrize("vpred", [False, True])

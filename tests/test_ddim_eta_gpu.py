@@ -16,25 +16,16 @@ profiles/LAB_NOTES.md ("Stochastic DDIM") holds a measured value; a float32 host
 new kernels at 1.1 - 1.3x the existing kernel's relative error (4e-8 .. 6e-8) and at most 2.4x its largest element error.
 """
 import os
-import subprocess
-import sys
-import time
-import xml.etree.ElementTree as ET
 
 import pytest
 import torch
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
-import ddim_eta_ref as R  # noqa: E402
-
-from view_neti_amd import lib as _lib  # noqa: E402  (ctypes only: importing it loads no library and touches no GPU)
+from helpers import ddim_eta_ref as R
+from helpers.bf16_child import run_bf16_child
+from helpers.checks import DEV, DT, TOL16, gen as _gen  # TOL16: unit roundoff of DT over fp16's (the factor behind t16)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEV = "cuda"
-DT = _lib.act_dtype()
-TOL16 = 8.0 if DT == torch.bfloat16 else 1.0  # unit roundoff of DT over fp16's (tests/test_kernels_gpu.py::t16)
 MARGIN = 4.0
 STEPS = 5  # the 5-step DDIM schedule on the SD scaled_linear betas: timesteps 801, 601, 401, 201, 1
 
@@ -274,10 +265,7 @@ def _pipeline(cfg_name, B):
     return _engines[(cfg_name, B)]
 
 
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
+# (not helpers.checks.frob_rel: this one compares in float64)
 def _rel(a, b):
     a, b = a.double().cpu(), b.double().cpu()
     return ((a - b).norm() / (b.norm() + 1e-20)).item()
@@ -437,22 +425,6 @@ def test_eta_with_dpm_solver_raises():
 def test_every_case_against_the_bf16_library(tmp_path):
     """the cases above in a child process with VNETI_PRECISION=bf16 (libvneti_hip_bf16.so); one child, under its own time
     limit, nothing retried"""
-    me = os.path.join("tests", os.path.basename(__file__))
-    expr = "not bf16_library"
-    cmd = [sys.executable, "-m", "pytest", me, "-m", "gpu", "-q", "-s", "-p", "no:cacheprovider", "-k", expr]
-    env = dict(os.environ, VNETI_PRECISION="bf16")
-    c = subprocess.run(cmd + ["--collect-only"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=120)
-    ids = [line.strip() for line in c.stdout.splitlines() if "::" in line]
-    assert c.returncode == 0 and len(ids) >= 30, c.stdout[-2000:] + c.stderr[-2000:]
-    xml = tmp_path / "junit.xml"
-    t0 = time.time()
-    r = subprocess.run(cmd + [f"--junitxml={xml}"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=170)
-    tail = r.stdout[-6000:] + "\n" + r.stderr[-2000:]
-    print(f"[ddim eta bf16] rc {r.returncode}, {len(ids)} collected, {time.time() - t0:.1f} s")
-    print("\n".join(l for l in r.stdout.splitlines() if l.startswith("[") or l.startswith("    eta")))
-    assert r.returncode == 0 and xml.exists(), tail
-    suite = ET.parse(xml).getroot()
-    suite = suite if suite.tag == "testsuite" else suite.find("testsuite")
-    tests, errors, failures, skipped = (int(suite.get(k, 0)) for k in ("tests", "errors", "failures", "skipped"))
-    assert errors == 0 and failures == 0 and skipped == 0 and tests == len(ids), \
-        f"bf16: {tests} run of {len(ids)}, {failures} failed, {errors} errors, {skipped} skipped\n{tail}"
+    out = run_bf16_child(os.path.join("tests", os.path.basename(__file__)), "not bf16_library", 170, tmp_path, least=30,
+                         extra_args=("-s",), collect_limit=120, what="ddim eta bf16")
+    print("\n".join(l for l in out.splitlines() if l.startswith("[") or l.startswith("    eta")))

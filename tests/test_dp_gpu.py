@@ -10,6 +10,8 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+from helpers.engines import STATES_FIRST, build_train_engine, feed_host_noise
+
 pytestmark = pytest.mark.gpu
 
 STEPS, B, H, W, LR = 3, 2, 64, 64, 3e-3
@@ -18,41 +20,15 @@ SCENES = [0, 2, 0]
 
 
 def _build(world, accum, mode3):
-    from view_neti_amd import sd_config as sc, synth
-    from view_neti_amd.engine.step import TrainStepEngine
-    from view_neti_amd.mapper import fourier_frequencies, init_mapper_state
-    cfg = sc.tiny()
-    D = cfg.clip.hidden_size
     # identical mapper initialisation on every rank: the reference gets it from the torch.manual_seed(0) inside every
     # FourierPositionalEncodingNDims constructor (App. C Q1); init_mapper_state draws from the global generator
-    torch.manual_seed(0)
-    gen = torch.Generator().manual_seed(7)
-    mk = lambda: {k: v + 0.05 * torch.randn(v.shape, generator=gen) for k, v in init_mapper_state(64, 64, D).items()}
-    objs = [mk() for _ in range(3 if mode3 else 1)]
-    kw = {}
-    if mode3:
-        kw = dict(mapper_view=mk(), w_enc_view=fourier_frequencies([0.03, 2.0] + [0.5] * 12, 64, 0), norm_scale_view=0.35,
-                  alpha_view=0.3)
-    eng = TrainStepEngine(cfg, synth.unet_weights(cfg.unet), synth.vae_weights(cfg.vae), synth.clip_weights(cfg.clip), B,
-                          H, W, objs if mode3 else objs[0], fourier_frequencies([0.03, 2.0], 64, 0), 0.4, 0.2, lr=LR,
-                          world_size=world, grad_accum=accum, device_rng=False, **kw)
+    cfg, eng, _, _, _, _ = build_train_engine("tiny", B, H, W, n_obj=3 if mode3 else 1, with_view=mode3, perturb_seed=7,
+                                              order=STATES_FIRST, lr=LR, world_size=world, grad_accum=accum, device_rng=False)
     return cfg, eng
 
 
 def _feed(cfg, eng, step, shard, mode3):
-    """micro-batch `shard` (= the rank in the DP run) of optimizer step `step`: host-supplied data and noise"""
-    from view_neti_amd import synth
-    s = 100 * step + 10 * shard
-    ph, phv = cfg.clip.vocab_size - 3, cfg.clip.vocab_size - 4
-    ids = synth.input_ids(B, ph, cfg.clip.vocab_size, view_placeholder_id=phv if mode3 else None)
-    px = synth.gaussian((B, 3, H, W), s + 1).clamp(-1, 1)
-    if mode3:
-        eng.set_batch(px, ids, torch.full((B,), ph), torch.full((B,), phv), synth.gaussian((B, 12), s + 2).clamp(-1, 1),
-                      object_index=SCENES[step])
-    else:
-        eng.set_batch(px, ids, torch.full((B,), ph))
-    t = torch.randint(0, 1000, (B,), generator=torch.Generator().manual_seed(s + 3))
-    eng.set_noise(synth.gaussian((B, 4, H // 8, W // 8), s + 4), synth.gaussian((B, 4, H // 8, W // 8), s + 5), t)
+    feed_host_noise(cfg, eng, step, shard, mode3, SCENES)
 
 
 def _worker(rank, world, port, mode3, out):

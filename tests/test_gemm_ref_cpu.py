@@ -4,23 +4,16 @@ at float64 agreement, <= 1e-12 relative.  The launches are real `functools.parti
 tensors — they are only read, never called — with the packed weights the engines use (packing.conv3x3_fwd / conv3x3_dgrad /
 _chunk_major / geglu_interleave)."""
 import math
-import os
-import sys
 from functools import partial
 
 import pytest
 import torch
 import torch.nn.functional as F
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
-import gemm_ref as G  # noqa: E402
+from helpers import gemm_ref as G
+from helpers.checks import ops as _ops
 
 TOL = 1e-12
-
-
-def _ops():
-    from view_neti_amd import ops
-    return ops
 
 
 def rnd(*shape, seed=0, scale=1.0):

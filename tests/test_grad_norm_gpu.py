@@ -3,42 +3,28 @@ through the C ABI: vneti_grad_sumsq + vneti_grad_norm_finish, vneti_adamw_flat_c
 vneti_train_record.
 
 References.  The norm: torch.linalg.vector_norm of the float64 gradient.  Clipped AdamW: the real torch.optim.AdamW on
-float64 CPU parameters with torch.nn.utils.clip_grad_norm_ before every step.  Bars: `check32` of tests/test_optim_rng_gpu.py
+float64 CPU parameters with torch.nn.utils.clip_grad_norm_ before every step.  Bars: `check32` of tests/helpers/checks.py
 (1e-5 unless 8 x the error of the same computation in torch float32 is larger); nothing comes from a kernel's output.  The
 kernels are f32 / f64 only, so one bar holds in both builds; `test_bf16_library_runs_this_file` runs every case against
 libvneti_hip_bf16.so in a child process, as tests/test_kernels_bf16_gpu.py does for the other kernel files."""
 import math
 import os
-import subprocess
-import sys
-import xml.etree.ElementTree as ET
 
 import pytest
 import torch
 
-from test_kernels_gpu import DEV, check  # noqa: F401  (tests/ is on sys.path: rootdir imports)
-from test_optim_rng_gpu import (ACTIVITY, N_FLAT, N_SEG, SEG_LEN, Scaler, check32, hyper_dev, i32, spread_gradients,
-                                torch_adamw)
-
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
-import slabs as S  # noqa: E402
+from helpers import slabs as S
+from helpers.adamw_ref import ACTIVITY, N_FLAT, N_SEG, SEG_LEN, hyper_dev, i32, spread_gradients, torch_adamw
+from helpers.bf16_child import run_bf16_child
+from helpers.checks import DEV, check32
+from helpers.checks import gen as _gen, ops as _ops
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32, F64 = torch.float32, torch.float64
 C = 4096          # the chunk of vneti_grad_sumsq's fixed partition (asserted below through the workspace query)
 SCALE = 65536.0   # the loss scale of the inputs: a power of two, so scaling is exact
 QNAN64 = 0x7FF8000000000000
 SENT64 = 0x7FF8A5A5A5A5A5A5
-
-
-def _ops():
-    from view_neti_amd import ops
-    return ops
-
-
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
 
 
 def _dev(x, dtype=F32):
@@ -497,15 +483,4 @@ def test_bf16_library_runs_this_file(tmp_path):
     from view_neti_amd import lib
     if lib.precision() == "bf16":
         return  # this IS the bf16 run
-    me, report = os.path.join("tests", os.path.basename(__file__)), str(tmp_path / "bf16.xml")
-    base = [sys.executable, "-m", "pytest", me, "-m", "gpu", "-q", "-p", "no:cacheprovider", "-k", "not bf16_library"]
-    env = dict(os.environ, VNETI_PRECISION="bf16")
-    listed = subprocess.run(base + ["--collect-only"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
-    want = sum(1 for line in listed.stdout.splitlines() if "::test_" in line)
-    assert listed.returncode == 0 and want >= 40, listed.stdout[-2000:]
-    r = subprocess.run(base + [f"--junitxml={report}"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
-    suite = ET.parse(report).getroot()
-    suite = suite if suite.tag == "testsuite" else suite.find("testsuite")
-    counts = {k: int(suite.get(k, 0)) for k in ("tests", "failures", "errors", "skipped")}
-    assert r.returncode == 0 and counts == {"tests": want, "failures": 0, "errors": 0, "skipped": 0}, \
-        (counts, want, r.stdout[-3000:])
+    run_bf16_child(os.path.join("tests", os.path.basename(__file__)), "not bf16_library", 240, tmp_path, least=40)

@@ -6,7 +6,6 @@ import math
 import os
 import subprocess
 import sys
-import xml.etree.ElementTree as ET
 from pathlib import Path
 
 import numpy as np
@@ -14,9 +13,14 @@ import pytest
 import torch
 from PIL import Image
 
+from helpers.bf16_child import run_bf16_child
+from helpers.checks import DEV
+from helpers.coach_runs import dtu_scene as _dtu_scene, mode2_cfg as _mode2_cfg, train_from_cfg as _train
+from helpers.engines import INIT_ALL_FIRST, STATE_PLUS as _STATE_PLUS, batch_dict as _batch, build_train_engine
+from helpers.engines import feed_dict as _set, snapshot
+
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
 ROOT = Path(__file__).resolve().parents[1]
 
 # ================================================================================================ kernel
@@ -128,56 +132,15 @@ def test_mse_per_sample_bf16_library(tmp_path):
     from view_neti_amd import lib
     if lib.precision() == "bf16":
         return  # the whole file run under VNETI_PRECISION=bf16: the cases above already were the bf16 run
-    expr = "mse_per_sample and not bf16_library"
-    xml = tmp_path / "junit.xml"
-    cmd = [sys.executable, "-m", "pytest", str(Path("tests") / "test_heldout_gpu.py"), "-m", "gpu", "-q", "-p",
-           "no:cacheprovider", "-k", expr, f"--junitxml={xml}"]
-    r = subprocess.run(cmd, cwd=str(ROOT), env=dict(os.environ, VNETI_PRECISION="bf16"), capture_output=True, text=True,
-                       timeout=120)
-    tail = r.stdout[-4000:] + "\n" + r.stderr[-2000:]
-    assert r.returncode == 0 and xml.exists(), f"bf16 child rc {r.returncode}\n{tail}"
-    suite = ET.parse(xml).getroot()
-    suite = suite if suite.tag == "testsuite" else suite.find("testsuite")
-    tests, errors, failures, skipped = (int(suite.get(k, 0)) for k in ("tests", "errors", "failures", "skipped"))
-    n_cases = len(SHAPES) + 3 + 1 + 1
-    assert (tests, errors, failures, skipped) == (n_cases, 0, 0, 0), tail
+    run_bf16_child(str(Path("tests") / "test_heldout_gpu.py"), "mse_per_sample and not bf16_library", 120, tmp_path,
+                   least=len(SHAPES) + 5, expect=len(SHAPES) + 3 + 1 + 1)
 
 
 # ================================================================================================ engine
 def _build(cfg_name, B, H=64, W=64, **kw):
-    """object + view mapper on the tiny shape families (the builder of tests/test_step_gpu.py)"""
-    from view_neti_amd import sd_config as sc, synth
-    from view_neti_amd.engine.step import TrainStepEngine
-    from view_neti_amd.mapper import fourier_frequencies, init_mapper_state
-    cfg = sc.CONFIGS[cfg_name]()
-    uw, vw, cw = synth.unet_weights(cfg.unet), synth.vae_weights(cfg.vae), synth.clip_weights(cfg.clip)
-    D = cfg.clip.hidden_size
-    with torch.random.fork_rng(devices=[]):
-        torch.manual_seed(0)
-        w_enc = fourier_frequencies([0.03, 2.0], 64, 0)
-        sd, sdv = init_mapper_state(64, 64, D), init_mapper_state(64, 64, D)
-    gen = torch.Generator().manual_seed(1)
-    sd = {k: v + 0.05 * torch.randn(v.shape, generator=gen) for k, v in sd.items()}
-    sdv = {k: v + 0.05 * torch.randn(v.shape, generator=gen) for k, v in sdv.items()}
-    w_enc_v = fourier_frequencies([0.03, 2.0] + [0.5] * 12, 64, 0)
-    extra = dict(mapper_view=sdv, w_enc_view=w_enc_v, norm_scale_view=0.35, alpha_view=0.3)
+    """object + view mapper on the tiny shape families, the global generator left as it was found"""
     kw.setdefault("lr", 1e-3)
-    eng = TrainStepEngine(cfg, uw, vw, cw, B, H, W, sd, w_enc, 0.4, 0.2, **extra, **kw)
-    return cfg, eng, (uw, vw, cw), sd, w_enc, extra
-
-
-def _batch(cfg, B, H=64, W=64, seed=0):
-    from view_neti_amd import synth
-    V = cfg.clip.vocab_size
-    ph, phv = V - 3, V - 4
-    return dict(px=synth.pixel_values(B, H, W, seed=1 + seed), ids=synth.input_ids(B, ph, V, view_placeholder_id=phv),
-                po=torch.full((B,), ph), pv=torch.full((B,), phv), vp=synth.gaussian((B, 12), 9 + seed).clamp(-1, 1),
-                t=synth.timesteps(B, seed=2 + seed), eps=synth.gaussian((B, 4, H // 8, W // 8), 3 + seed),
-                noise=synth.gaussian((B, 4, H // 8, W // 8), 4 + seed))
-
-
-def _set(eng, b, for_eval=False, **kw):
-    eng.set_batch(b["px"], b["ids"], b["po"], b["pv"], b["vp"], for_eval=for_eval, **kw)
+    return build_train_engine(cfg_name, B, H, W, with_view=True, fork_rng=True, order=INIT_ALL_FIRST, **kw)
 
 
 def _eval(eng, b, graph=True):
@@ -186,12 +149,9 @@ def _eval(eng, b, graph=True):
     return eng.eval_losses(graph=graph)
 
 
-_STATE_PLUS = ("params", "exp_avg", "exp_avg_sq", "opt_step", "seg_step", "scaler", "rng_state", "hyper", "grads", "loss_sum")
-
-
 def _snapshot(eng):
     assert set(eng._STATE) <= set(_STATE_PLUS)
-    return {n: getattr(eng, n).clone() for n in _STATE_PLUS}
+    return snapshot(eng, _STATE_PLUS)
 
 
 @pytest.mark.parametrize("cfg_name", ["tiny", "tiny21"])
@@ -319,53 +279,6 @@ def test_eval_losses_inside_an_accumulation_group_raise():
 
 
 # ================================================================================================ Coach
-def _dtu_scene(root: Path, scans, seed=1):
-    cal = root / "data" / "dtu" / "Calibration" / "cal18"
-    cal.mkdir(parents=True)
-    rng = np.random.RandomState(seed)
-    mats = rng.randn(49, 3, 4) * np.array([[1e3, 1e3, 1e3, 1e5]])
-    for i in range(49):
-        np.savetxt(cal / f"pos_{i + 1:03d}.txt", mats[i])
-    from view_neti_amd.compat.dataset import TextualInversionDataset
-    out = []
-    for scan in scans:
-        d = root / "data" / "dtu" / "Rectified" / scan
-        d.mkdir(parents=True)
-        for c in range(49):
-            Image.fromarray(rng.randint(0, 255, (120, 160, 3), dtype=np.uint8)).save(
-                d / TextualInversionDataset.dtu_cam_and_lighting_to_fname(c, "3"))
-        out.append(d)
-    return out
-
-
-def _mode2_cfg(scan, out, name, *extra):
-    from view_neti_amd.compat import config as C
-    cfg = C.parse(C.RunConfig, [
-        "--learnable_mode", "2", "--data.train_data_dir", str(scan), "--data.placeholder_object_token", "<object>",
-        "--data.camera_representation", "dtu-12d", "--data.dtu_subset", "3", "--data.dtu_preprocess_key", "1",
-        "--data.augmentation_key", "5", "--data.dataloader_num_workers", "0", "--model.word_embedding_dim", "128",
-        "--model.arch_view_net", "15", "--model.arch_view_disable_tl", "False", "--model.arch_mlp_hidden_dims", "64",
-        "--model.use_nested_dropout", "True", "--model.pe_sigma_exp_key", "2", "--optim.max_train_steps", "4",
-        "--optim.train_batch_size", "3", "--optim.gradient_accumulation_steps", "1", "--optim.mixed_precision", "fp16",
-        "--log.save_steps", "2", "--eval.validation_steps", "1000", "--eval.num_denoising_steps", "2",
-        "--eval.num_validation_images", "1", "--eval.validation_seeds", "[0]", "--log.exp_dir", str(out),
-        "--log.exp_name", name, *extra])
-    cfg.log.exp_dir = cfg.log.exp_dir / cfg.log.exp_name
-    cfg.log.logging_dir = cfg.log.exp_dir / cfg.log.logging_dir
-    return cfg
-
-
-def _train(cfg):
-    from view_neti_amd.compat.coach import Coach
-    import random
-    torch.manual_seed(cfg.seed)
-    np.random.seed(0)
-    random.seed(0)
-    coach = Coach(cfg)
-    coach.train()
-    return coach
-
-
 def _close(a, b, rel):
     if isinstance(a, dict):
         assert a.keys() == b.keys()

@@ -3,12 +3,9 @@
 import pytest
 import torch
 
+from helpers.checks import frob_rel as _rel
+
 pytestmark = pytest.mark.gpu
-
-
-def _rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / (b.norm() + 1e-20)).item()
 
 
 @pytest.mark.parametrize("B,h,w", [(1, 8, 8), (2, 8, 16)])

@@ -21,25 +21,17 @@ Precision-generic like tests/test_kernels_gpu.py (the bf16 build runs it through
 case passes its workspace explicitly; the process-wide default workspace is set aside for the duration of a case, so the
 file neither depends on nor changes the order of the tests."""
 import math
-import os
-import sys
 
 import pytest
 import torch
 import torch.nn.functional as F
 
-from test_kernels_gpu import DEV, DT, check, t16, rnd  # the kernel file's helpers (tests/ is on sys.path: rootdir imports)
-
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
-import slabs as S  # noqa: E402
+from helpers import slabs as S
+from helpers.checks import DEV, DT, check, t16, rnd  # the kernel files' bars
+from helpers.checks import attn_ref as _attn_ref, ops as _ops
 
 pytestmark = pytest.mark.gpu
 F32 = torch.float32
-
-
-def _ops():
-    from view_neti_amd import ops
-    return ops
 
 
 @pytest.fixture(autouse=True)
@@ -617,9 +609,6 @@ def test_contract_norm_transpose_multi():
 
 
 # ------------------------------------------------------------------------------------------ attention
-from test_kernels_gpu import _attn_ref  # noqa: E402
-
-
 def _attention_case(D, Nq, Nk, causal, use_ws, small=False):
     """fwd, attn_bwd_delta, attn_bwd_dq in both delta forms, attn_bwd_dkv (and attn_bwd_small): every operand in a slab of
     its own with ld = H * D + 24, + 32, ...; the spike key of the parity test keeps the online-softmax rescale path in"""

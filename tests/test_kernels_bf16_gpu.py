@@ -8,23 +8,22 @@ limit of its own; a group belongs to one file).  tests/test_bf16_gpu.py checks w
 with bars that see an O(1) error; here every tile hint, conv K order, split-K path, norm shape, attention head dim and elementwise kernel of the bf16
 machine code is compared with its fp32 reference at the fp16 tolerance times 8 (see the kernel file's docstring).
 
-What a parent test asserts from the child's junit report: errors = 0, failures = 0, SKIPPED = 0 and tests run == the
-number the same `-k` expression collects — a child that found no GPU (everything skipped), a typo in `-k` (nothing
-selected) or a crash halfway cannot pass as "0 failed".  `test_groups_cover_the_kernel_file` proves, for every kernel file,
-that its groups are disjoint and that their union is the file's whole collection, so no kernel test is left out of the bf16 run.
+The child runner is tests/helpers/bf16_child.py, shared with the other files that re-run themselves in bf16.  What it
+asserts from the child's junit report: errors = 0, failures = 0, SKIPPED = 0 and tests run == the number the same `-k`
+expression collects — a child that found no GPU (everything skipped), a typo in `-k` (nothing selected) or a crash halfway
+cannot pass as "0 failed".  `test_groups_cover_the_kernel_file` proves, for every kernel file, that its groups are disjoint
+and that their union is the file's whole collection, so no kernel test is left out of the bf16 run.
 
 Shared-machine shape: the children run one at a time (parent + one child on the GPU, never more), each under its own
-time limit; nothing is retried; once a child has died (signal, abort, time limit) the remaining groups FAIL at once
-without starting a process — a GPU that has just faulted is not handed further work."""
+time limit; nothing is retried; once a child has died (signal, abort, time limit) the remaining groups, and the bf16
+children of every other file, FAIL at once without starting a process — a GPU that has just faulted is not handed further
+work."""
 import os
-import subprocess
-import sys
-import time
-import xml.etree.ElementTree as ET
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from helpers.bf16_child import collect as _collect, run_bf16_child
+
 KERNEL_FILE = os.path.join("tests", "test_kernels_gpu.py")
 TEXT_FILE = os.path.join("tests", "test_text_kernels_gpu.py")
 OPTIM_RNG_FILE = os.path.join("tests", "test_optim_rng_gpu.py")
@@ -55,29 +54,6 @@ GROUPS = {
 }
 # kernel file -> the least number of cases its collection must hold (a file that lost its tests cannot pass as "covered")
 KERNEL_FILES = {KERNEL_FILE: 500, TEXT_FILE: 120, OPTIM_RNG_FILE: 30, CONTRACTS_FILE: 100, VARIANTS_FILE: 11}
-DEATH_CODES = (124, 134, 137, 139)  # time limit, abort, kill, segmentation fault (a negative code is a signal)
-
-_dead = None        # "group X died with rc N": set once, read by every later group
-_collected = {}     # (kernel file, `-k` expression (None: the whole file)) -> collected test ids
-
-
-def _pytest_cmd(path, *extra):
-    return [sys.executable, "-m", "pytest", path, "-m", "gpu", "-q", "-p", "no:cacheprovider", *extra]
-
-
-def _env():
-    return dict(os.environ, VNETI_PRECISION="bf16")  # added to the inherited environment, nothing removed
-
-
-def _collect(path, expr=None):
-    """ids `--collect-only` lists (touches no GPU: the kernel files import view_neti_amd.ops lazily)"""
-    if (path, expr) not in _collected:
-        r = subprocess.run(_pytest_cmd(path, "--collect-only", *(["-k", expr] if expr else [])), cwd=ROOT, env=_env(),
-                           capture_output=True, text=True, timeout=240)
-        assert r.returncode == 0, \
-            f"collecting {path} {expr!r} failed (rc {r.returncode}):\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}"
-        _collected[(path, expr)] = [line.strip() for line in r.stdout.splitlines() if "::" in line]
-    return _collected[(path, expr)]
 
 
 def test_groups_cover_the_kernel_file():
@@ -103,33 +79,5 @@ def test_groups_cover_the_kernel_file():
 @pytest.mark.gpu
 @pytest.mark.parametrize("group", list(GROUPS))
 def test_kernels_bf16(group, tmp_path):
-    global _dead
-    assert _dead is None, f"not run: {_dead}"
     path, expr, limit = GROUPS[group]
-    n_collected = len(_collect(path, expr))
-    assert n_collected > 0
-    xml = tmp_path / "junit.xml"
-    t0 = time.time()
-    try:
-        r = subprocess.run(_pytest_cmd(path, "-k", expr, f"--junitxml={xml}"), cwd=ROOT, env=_env(), capture_output=True, text=True,
-                           timeout=limit)
-    except subprocess.TimeoutExpired as e:
-        _dead = f"group {group} died with rc TimeoutExpired ({limit} s)"
-        out = e.stdout.decode(errors="replace") if isinstance(e.stdout, bytes) else (e.stdout or "")
-        raise AssertionError(f"bf16 {group}: no end after {limit} s\n{out[-3000:]}")
-    rc, tail = r.returncode, (r.stdout[-6000:] + "\n" + r.stderr[-2000:])
-    print(f"[bf16 kernels] group {group}: rc {rc}, {n_collected} collected, {time.time() - t0:.1f} s")
-    if rc < 0 or rc in DEATH_CODES:
-        _dead = f"group {group} died with rc {rc}"
-        raise AssertionError(f"bf16 {group}: the child died with rc {rc}\n{tail}")
-    assert xml.exists(), f"bf16 {group}: no junit report (rc {rc})\n{tail}"
-    suite = ET.parse(xml).getroot()
-    suite = suite if suite.tag == "testsuite" else suite.find("testsuite")
-    tests, errors, failures, skipped = (int(suite.get(k, 0)) for k in ("tests", "errors", "failures", "skipped"))
-    bad = [f"{c.get('classname')}::{c.get('name')} ({kind})" for c in suite.iter("testcase")
-           for kind in ("failure", "error", "skipped") if c.find(kind) is not None]
-    print(f"[bf16 kernels] group {group}: {tests} run, {failures} failed, {errors} errors, {skipped} skipped")
-    assert errors == 0 and failures == 0 and skipped == 0, \
-        f"bf16 {group}: {failures} failed, {errors} errors, {skipped} skipped of {tests}:\n" + "\n".join(bad[:60]) + "\n" + tail
-    assert tests == n_collected, f"bf16 {group}: {tests} tests ran, `-k {expr}` collects {n_collected}\n{tail}"
-    assert rc == 0, f"bf16 {group}: rc {rc}\n{tail}"
+    run_bf16_child(path, expr, limit, tmp_path, least=1, what=f"bf16 kernels group {group}")

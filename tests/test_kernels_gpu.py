@@ -14,55 +14,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from helpers.checks import DEV, DT, check, rnd, t16  # DT, t16 and check: the rules above, in tests/helpers/checks.py
+from helpers.checks import attn_ref as _attn_ref, ops as _ops
 from view_neti_amd import lib as _lib  # (ctypes only: importing it loads no library and touches no GPU)
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda"
-DT = _lib.act_dtype()                         # torch.float16, or torch.bfloat16 under VNETI_PRECISION=bf16
-TOL16 = 8.0 if DT == torch.bfloat16 else 1.0  # unit roundoff of DT over fp16's
-
-
-def t16(tol):
-    """the tolerance of a check through a 16-bit store: the stated fp16 number, times 8 in bf16"""
-    return tol * TOL16
-
-
-def _ops():
-    from view_neti_amd import ops
-    return ops
-
-
-def rnd(*shape, scale=1.0, seed=0, dtype=None):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randn(*shape, generator=g) * scale).to(DT if dtype is None else dtype)
-
-
-def relerr(a, b):
-    a = a.float().cpu()
-    b = b.float().cpu()
-    return ((a - b).norm() / (b.norm() + 1e-12)).item(), (a - b).abs().max().item()
-
-
-ELEM_K = 8.0
-
-
-def check(name, got, ref, tol, elem_k=ELEM_K):
-    """two bounds: the relative Frobenius norm (< tol), and an ELEMENT-WISE one so that a wrong tail row / column of a
-    large output cannot hide inside the norm: |got - ref| <= elem_k * tol * (rms(ref) + |ref|) for every element
-    (f16 rounding scales with the element, accumulation noise with the tensor's rms; a Gaussian error of sigma =
-    tol * rms stays under 6 sigma over 1e7 elements, a dropped or misplaced element is off by ~|ref| itself)."""
-    a, b = got.float().cpu(), ref.float().cpu()
-    r, m = relerr(a, b)
-    rms = b.pow(2).mean().sqrt()
-    excess = (a - b).abs() - elem_k * tol * (rms + b.abs())
-    worst = excess.max().item()
-    print(f"[{name}] rel={r:.3e} maxabs={m:.3e} elem-bound margin={-worst:.3e}")
-    assert math.isfinite(r) and r < tol, f"{name}: rel err {r} (max abs {m}) >= {tol}"
-    if worst > 0:
-        idx = [int(i) for i in torch.unravel_index(excess.argmax(), excess.shape)]
-        raise AssertionError(f"{name}: element {idx} off by {(a - b)[tuple(idx)].item():.4e} (ref {b[tuple(idx)].item():.4e}, "
-                             f"rms {rms.item():.3e}): beyond the element-wise bound {elem_k}*{tol}*(rms+|ref|)")
 
 
 # ------------------------------------------------------------------------------------------ GEMM
@@ -592,22 +548,6 @@ def test_transpose_and_softmax():
 
 
 # ------------------------------------------------------------------------------------------ attention
-def _attn_ref(q, k, v, H, D, scale, causal):
-    Bn, Nq, _ = q.shape
-    Nk = k.shape[1]
-    qh = q.view(Bn, Nq, H, D).transpose(1, 2)
-    kh = k.view(Bn, Nk, H, D).transpose(1, 2)
-    vh = v.view(Bn, Nk, H, D).transpose(1, 2)
-    s = (qh @ kh.transpose(-1, -2)) * scale
-    if causal:
-        mask = torch.ones(Nq, Nk, dtype=torch.bool).tril()
-        s = s.masked_fill(~mask, float("-inf"))
-    p = torch.softmax(s, -1)
-    o = (p @ vh).transpose(1, 2).reshape(Bn, Nq, H * D)
-    lse = torch.logsumexp(s, -1)
-    return o, lse
-
-
 @pytest.mark.parametrize("D,H,Nq,Nk,causal", [
     (40, 8, 200, 200, False), (40, 2, 300, 77, False), (64, 12, 77, 77, True), (80, 8, 128, 77, False),
     (160, 8, 256, 256, False), (160, 2, 64, 77, False), (64, 3, 200, 200, True), (80, 2, 520, 520, False),

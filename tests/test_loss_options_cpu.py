@@ -3,18 +3,15 @@ compare against (tests/helpers/loss_options_ref.py), the configuration fields, w
 fingerprint, and `loss_weighted` in train-metrics.jsonl.  No GPU."""
 import json
 import math
-import os
-import sys
 
 import pytest
 import torch
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
-import loss_options_ref as LR  # noqa: E402
+from helpers import loss_options_ref as LR
 
-from view_neti_amd.compat import config as C  # noqa: E402
-from view_neti_amd.compat import resume as R  # noqa: E402
-from view_neti_amd.compat import train_metrics as TM  # noqa: E402
+from view_neti_amd.compat import config as C
+from view_neti_amd.compat import resume as R
+from view_neti_amd.compat import train_metrics as TM
 
 AC = LR.scaled_linear_alphas_cumprod_f32()
 ALL_T = torch.arange(1000)

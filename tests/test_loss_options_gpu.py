@@ -10,32 +10,23 @@ kernel cases (test_kernel_*) also run against libvneti_hip_bf16.so in a child pr
 import json
 import math
 import os
-import subprocess
-import sys
-import xml.etree.ElementTree as ET
 
 import pytest
 import torch
 
-import test_resume_gpu as rt          # the tiny Coach builders (tests/ is on sys.path: rootdir imports)
-import test_train_metrics_gpu as tm   # the tiny engine builders with the engine's keyword arguments open
-from test_kernels_gpu import DEV, DT, check, rnd, t16
-from test_step_gpu import build as build_step
-
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
-import loss_options_ref as LR  # noqa: E402
+from helpers import coach_runs as rt  # the tiny Coach runs: toys, mode0_cfg, coach, train_counting
+from helpers import loss_options_ref as LR
+from helpers.bf16_child import run_bf16_child
+from helpers.checks import DEV, DT, check, rnd, t16, ops as _ops
+from helpers.engines import FORMS, STATE, build_device_rng_engine as _build, build_train_engine as build_step
+from helpers.engines import feed_device_rng, feed_six as _feed, run_steps, six_steps as _six_steps, snapshot
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = torch.float32
 GAMMA, OFFSET = 5.0, 0.1
 AC = LR.scaled_linear_alphas_cumprod_f32()   # the f32 table: the shared input of kernel and reference
-STATE = tm.STATE
-
-
-def _ops():
-    from view_neti_amd import ops
-    return ops
+B, H, W = 2, 64, 64   # of the device-RNG engines (helpers.engines.build_device_rng_engine)
+ROWS = 16
 
 
 # ================================================================================================ kernel: mse_loss_grad_snr
@@ -172,18 +163,7 @@ def test_bf16_library_runs_the_kernel_cases(tmp_path):
     from view_neti_amd import lib
     if lib.precision() == "bf16":
         return  # this IS the bf16 run
-    me, report = os.path.join("tests", os.path.basename(__file__)), str(tmp_path / "bf16.xml")
-    base = [sys.executable, "-m", "pytest", me, "-m", "gpu", "-q", "-p", "no:cacheprovider", "-k", "test_kernel_"]
-    env = dict(os.environ, VNETI_PRECISION="bf16")
-    listed = subprocess.run(base + ["--collect-only"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
-    want = sum(1 for line in listed.stdout.splitlines() if "::test_" in line)
-    assert listed.returncode == 0 and want >= 13, listed.stdout[-2000:]
-    r = subprocess.run(base + [f"--junitxml={report}"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
-    suite = ET.parse(report).getroot()
-    suite = suite if suite.tag == "testsuite" else suite.find("testsuite")
-    counts = {k: int(suite.get(k, 0)) for k in ("tests", "failures", "errors", "skipped")}
-    assert r.returncode == 0 and counts == {"tests": want, "failures": 0, "errors": 0, "skipped": 0}, \
-        (counts, want, r.stdout[-3000:])
+    run_bf16_child(os.path.join("tests", os.path.basename(__file__)), "test_kernel_", 240, tmp_path, least=13)
 
 
 # ================================================================================================ whole step vs the CPU oracle
@@ -263,7 +243,7 @@ def test_train_step_with_options_matches_oracle(cfg_name, with_view, H, W, snr_o
     relative error < 5e-2 (the bars of test_train_step_tiny_matches_oracle) — and NOT within them of the plain objective"""
     B = 2
     kw = dict(snr_gamma=GAMMA if snr_on else None, noise_offset=OFFSET if offset_on else None)
-    cfg, eng, weights, sd, w_enc, extra = build_step(cfg_name, B, H, W, with_view, device_rng=False, lr=4e-3, **kw)
+    cfg, eng, weights, sd, w_enc, extra = build_step(cfg_name, B, H, W, with_view=with_view, device_rng=False, lr=4e-3, **kw)
     _STEP_BUILDS.setdefault(cfg_name, (cfg, None, weights, sd, w_enc, extra))
     inp = _step_inputs(cfg, with_view, H, W)
     ph, phv = cfg.clip.vocab_size - 3, cfg.clip.vocab_size - 4
@@ -297,11 +277,11 @@ def test_train_step_with_options_matches_oracle(cfg_name, with_view, H, W, snr_o
 # ================================================================================================ engine behaviour
 def test_snr_gamma_inf_is_the_plain_training():
     """epsilon family, captured steps: every weight is exactly 1, so every state tensor is the plain engine's"""
-    plain, _, _ = tm._six_steps("one-mapper")
-    inf, _, _ = tm._six_steps("one-mapper", snr_gamma=math.inf)
+    plain, _, _ = _six_steps("one-mapper")
+    inf, _, _ = _six_steps("one-mapper", snr_gamma=math.inf)
     for f in STATE:
         assert torch.equal(plain[f], inf[f]), f"{f} differs with snr_gamma=inf"
-    five, _, _ = tm._six_steps("one-mapper", snr_gamma=GAMMA)
+    five, _, _ = _six_steps("one-mapper", snr_gamma=GAMMA)
     assert not torch.equal(plain["params"], five["params"]), "snr_gamma=5 must change the training"
     for f in ("rng_state", "opt_step"):
         assert torch.equal(plain[f], five[f])
@@ -310,14 +290,14 @@ def test_snr_gamma_inf_is_the_plain_training():
 def test_device_rng_streams():
     """stream 5 draws the offset; streams 0-2 draw what they always drew"""
     ops = _ops()
-    cfg, plain = tm._build(False, 1)
-    _, eng = tm._build(False, 1, noise_offset=OFFSET)
-    assert plain.offset_noise is None and tuple(eng.offset_noise.shape) == (tm.B, 4)
+    cfg, plain = _build(False, 1)
+    _, eng = _build(False, 1, noise_offset=OFFSET)
+    assert plain.offset_noise is None and tuple(eng.offset_noise.shape) == (B, 4)
     draws = []
     for s in range(2):
         state = eng.rng_state.clone()
         for e in (plain, eng):
-            tm._feed(cfg, e, s, 0, False)
+            _feed(cfg, e, s, 0, False)
             assert e.step()
         torch.cuda.synchronize()
         if s == 0:
@@ -347,43 +327,43 @@ _BOTH = dict(snr_gamma=GAMMA, noise_offset=OFFSET)
 def test_captured_replay_equals_eager_and_resumes(form):
     """both options on: 3 eager steps == 3 replayed steps; state_dict after 3 -> a fresh engine -> 3 more == 6 in one run;
     a state is refused by an engine without the option or with another value, naming the field"""
-    mode3 = tm.FORMS[form][0]
-    cfg, eager = tm._build(mode3, 1, **_BOTH)
+    mode3 = FORMS[form][0]
+    cfg, eager = _build(mode3, 1, **_BOTH)
     for s in range(3):
-        tm._feed(cfg, eager, s, 0, mode3)
+        _feed(cfg, eager, s, 0, mode3)
         assert eager.step_eager()
-    _, graph = tm._build(mode3, 1, **_BOTH)
-    tm._feed(cfg, graph, 0, 0, mode3)
+    _, graph = _build(mode3, 1, **_BOTH)
+    _feed(cfg, graph, 0, 0, mode3)
     graph.capture()
     assert graph.graph_a is not None
-    tm._steps(cfg, graph, range(3), mode3)
-    a, b = tm._state(eager), tm._state(graph)
+    run_steps(cfg, graph, range(3), mode3, _feed)
+    a, b = snapshot(eager, STATE), snapshot(graph, STATE)
     for f in STATE:
         assert torch.equal(a[f], b[f]), f"{form}: {f} differs between eager and replayed steps"
     assert eager.loss() == graph.loss()
     sd = graph.state_dict()
     assert sd["meta"]["snr_gamma"] == GAMMA and sd["meta"]["noise_offset"] == OFFSET
-    tm._steps(cfg, graph, range(3, 6), mode3)
-    want = tm._state(graph)
-    _, fresh = tm._build(mode3, 1, **_BOTH)
+    run_steps(cfg, graph, range(3, 6), mode3, _feed)
+    want = snapshot(graph, STATE)
+    _, fresh = _build(mode3, 1, **_BOTH)
     fresh.load_state_dict(sd)
-    tm._feed(cfg, fresh, 3, 0, mode3)
+    _feed(cfg, fresh, 3, 0, mode3)
     fresh.capture()
-    tm._steps(cfg, fresh, range(3, 6), mode3)
-    got = tm._state(fresh)
+    run_steps(cfg, fresh, range(3, 6), mode3, _feed)
+    got = snapshot(fresh, STATE)
     for f in STATE:
         assert torch.equal(want[f], got[f]), f"{form}: {f} differs after the resume"
     if mode3:
         return
     for field, other in (("snr_gamma", dict(_BOTH, snr_gamma=None)), ("snr_gamma", dict(_BOTH, snr_gamma=4.0)),
                          ("noise_offset", dict(_BOTH, noise_offset=None)), ("noise_offset", dict(_BOTH, noise_offset=0.2))):
-        _, e = tm._build(False, 1, **other)
+        _, e = _build(False, 1, **other)
         with pytest.raises(ValueError, match=field) as err:
             e.load_state_dict(sd)
         assert "n_params" not in str(err.value)
         with pytest.raises(ValueError, match=field):
             fresh.load_state_dict(e.state_dict())
-    _, plain = tm._build(False, 1)
+    _, plain = _build(False, 1)
     assert "snr_gamma" not in plain.state_dict()["meta"] and "noise_offset" not in plain.state_dict()["meta"]
 
 
@@ -391,39 +371,39 @@ def test_constructor_refuses_bad_values():
     for name in ("snr_gamma", "noise_offset"):
         for bad in (0.0, -1.0, math.nan):
             with pytest.raises(ValueError, match=name):
-                tm._build(False, 1, **{name: bad})
+                _build(False, 1, **{name: bad})
     with pytest.raises(ValueError, match="noise_offset"):
-        tm._build(False, 1, noise_offset=math.inf)
+        _build(False, 1, noise_offset=math.inf)
 
 
 def test_heldout_losses_and_the_ring_stay_unweighted():
     from view_neti_amd import synth
     ops = _ops()
-    cfg, plain = tm._build(False, 1)
-    _, eng = tm._build(False, 1, telemetry_rows=tm.ROWS, **_BOTH)
+    cfg, plain = _build(False, 1)
+    _, eng = _build(False, 1, telemetry_rows=ROWS, **_BOTH)
     assert torch.equal(plain.params, eng.params)
     eng.offset_noise.normal_()  # whatever the buffer holds, the evaluation does not read it
-    h, w = tm.H // 8, tm.W // 8
+    h, w = H // 8, W // 8
     losses = []
     for e in (plain, eng):
-        rt._feed(cfg, e, 0, 0, False)
+        feed_device_rng(cfg, e, 0, 0, False)
         ph = cfg.clip.vocab_size - 3
-        e.set_batch(synth.pixel_values(tm.B, tm.H, tm.W, seed=11), synth.input_ids(tm.B, ph, cfg.clip.vocab_size),
-                    torch.full((tm.B,), ph), for_eval=True)
-        e.set_noise(synth.gaussian((tm.B, 4, h, w), 13), synth.gaussian((tm.B, 4, h, w), 14), torch.tensor([40, 700]))
+        e.set_batch(synth.pixel_values(B, H, W, seed=11), synth.input_ids(B, ph, cfg.clip.vocab_size),
+                    torch.full((B,), ph), for_eval=True)
+        e.set_noise(synth.gaussian((B, 4, h, w), 13), synth.gaussian((B, 4, h, w), 14), torch.tensor([40, 700]))
         losses.append((e.eval_losses(graph=False), e.eval_losses(graph=True)))
     assert torch.equal(losses[0][0], losses[1][0]) and torch.equal(losses[0][1], losses[1][1])
     assert torch.equal(losses[0][0], losses[0][1]) and float(losses[0][0].min()) > 0
     # ---- the ring row of a training micro-step: plain per-sample MSE of the step's own pred / target.  Host-supplied
     # timesteps (40, 700), so that one sample's weight is not 1
-    cfg, eng, _, _, _, _ = build_step("tiny", tm.B, tm.H, tm.W, device_rng=False, lr=4e-3, telemetry_rows=tm.ROWS, **_BOTH)
-    inp = _step_inputs(cfg, False, tm.H, tm.W)
-    eng.set_batch(inp["px"], inp["ids"], torch.full((tm.B,), cfg.clip.vocab_size - 3))
+    cfg, eng, _, _, _, _ = build_step("tiny", B, H, W, device_rng=False, lr=4e-3, telemetry_rows=ROWS, **_BOTH)
+    inp = _step_inputs(cfg, False, H, W)
+    eng.set_batch(inp["px"], inp["ids"], torch.full((B,), cfg.clip.vocab_size - 3))
     eng.set_noise(inp["eps"], inp["noise"], inp["t"], offset_noise=inp["xi"])
     eng.forward_backward()
     Lc, hw = 4, h * w
-    direct, ws = torch.zeros(tm.B, device=DEV), torch.zeros_like(eng.eval_ws)
-    ops.mse_loss_per_sample(eng.unet.pred, eng.target, direct, ws, tm.B, Lc, hw)
+    direct, ws = torch.zeros(B, device=DEV), torch.zeros_like(eng.eval_ws)
+    ops.mse_loss_per_sample(eng.unet.pred, eng.target, direct, ws, B, Lc, hw)
     torch.cuda.synchronize()
     t = eng.timesteps.cpu()
     eng.optimizer_step()
@@ -443,11 +423,11 @@ def test_launch_counts(form, monkeypatch):
     """an eager step's ABI calls (one kernel launch each for the entries concerned): snr_gamma swaps one entry for the
     other and adds none; noise_offset swaps one and adds one rng_fill_normal; everything else is the plain list in order"""
     from view_neti_amd import lib
-    mode3 = tm.FORMS[form][0]
+    mode3 = FORMS[form][0]
 
     def calls(**kw):
-        cfg, eng = tm._build(mode3, 1, **kw)
-        tm._feed(cfg, eng, 0, 0, mode3)
+        cfg, eng = _build(mode3, 1, **kw)
+        _feed(cfg, eng, 0, 0, mode3)
         names, orig = [], lib.call
         with monkeypatch.context() as m:
             m.setattr(lib, "call", lambda name, *a: (names.append(name), orig(name, *a))[1])
@@ -473,12 +453,12 @@ def test_launch_counts(form, monkeypatch):
 
 # ================================================================================================ Coach
 def test_coach_run_with_both_options(tmp_path):
-    rt._toys(tmp_path / "toys")
+    rt.toys(tmp_path / "toys")
     on = ("--optim.snr_gamma", "5", "--optim.noise_offset", "0.1", "--log.train_metrics", "true")
-    cfg = rt._mode0_cfg(tmp_path / "toys", tmp_path / "a", *on, max_steps=3)
-    coach = rt._coach(cfg)
+    cfg = rt.mode0_cfg(tmp_path / "toys", tmp_path / "a", *on, max_steps=3)
+    coach = rt.coach(cfg)
     assert coach.engine.snr_gamma == 5.0 and coach.engine.noise_offset == 0.1
-    assert rt._train(coach) == 3
+    assert rt.train_counting(coach) == 3
     ck = torch.load(cfg.log.exp_dir / "mapper-steps-3_object.pt", map_location="cpu", weights_only=False)
     assert "snr_gamma" not in ck["cfg"]["optim"] and "noise_offset" not in ck["cfg"]["optim"]
     ext = ck["vneti_ext"]["config_ext"]
@@ -493,7 +473,7 @@ def test_coach_run_with_both_options(tmp_path):
     del coach
     # a run with another gamma, or without one, cannot continue this state: the field is named
     for other in (("--optim.snr_gamma", "4", "--optim.noise_offset", "0.1"), ("--optim.noise_offset", "0.1")):
-        cfg2 = rt._mode0_cfg(tmp_path / "toys", tmp_path / f"x{len(other)}", "--model.mapper_checkpoint_path",
+        cfg2 = rt.mode0_cfg(tmp_path / "toys", tmp_path / f"x{len(other)}", "--model.mapper_checkpoint_path",
                              str(cfg.log.exp_dir / "mapper-steps-3"), *other)
         with pytest.raises(ValueError, match="snr_gamma"):
-            rt._coach(cfg2)
+            rt.coach(cfg2)

@@ -2,15 +2,12 @@
 restatement (tests/helpers/lpips_ref.py) against a hand-written per-pixel evaluation, the InferenceConfig switches, and
 summarize_dtu on synthetic run directories with the restatement injected."""
 import csv
-import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
-import lpips_ref  # noqa: E402
+from helpers import lpips_ref
 
 
 def test_loaders_accept_reference_keys_and_reject_bad_ones(tmp_path):

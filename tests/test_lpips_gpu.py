@@ -2,16 +2,13 @@
 torch, the whole metric against the fp32 host restatement (tests/helpers/lpips_ref.py) at 60x84 and the 300x400 DTU
 evaluation size, its exact properties (identity, symmetry, reproducibility, position and sub-batch independence), and the
 DTU harness with do_lpips on a synthetic scene."""
-import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
-import lpips_ref  # noqa: E402
+from helpers import lpips_ref
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"

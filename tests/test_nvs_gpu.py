@@ -4,14 +4,11 @@ output-extent guards of the buffer-store launchers."""
 import pytest
 import torch
 
+from helpers.checks import frob_rel as _rel
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-
-
-def _rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / (b.norm() + 1e-20)).item()
 
 
 def _bucket(states, n_each):

@@ -4,7 +4,7 @@ the small inference helpers (conv1x1_nchw, table_fill_i64, counter_advance).
 
 References.  The optimizer: the real torch.optim.AdamW on float64 CPU parameters, driven with the f32-rounded
 hyper-parameters the kernel reads and the unscaled gradients; GradScaler's update rule (backoff 0.5, growth 2,
-growth_interval) is restated in `Scaler` below.  The RNG: `hash_u32` and the index formulas restated with numpy uint64
+growth_interval) is restated in `Scaler` (tests/helpers/adamw_ref.py).  The RNG: `hash_u32` and the index formulas restated with numpy uint64
 masking — the integer outputs (timesteps, dropout masks) must be EQUAL; the normals are compared with the float64
 Box-Muller of the same uniforms, and the statistics of the device output (not of the restatement) are bounded in standard
 errors.
@@ -21,86 +21,15 @@ import numpy as np
 import pytest
 import torch
 
-from test_kernels_gpu import DEV, check  # the kernel file's helpers (tests/ is on sys.path: rootdir imports)
+from helpers.adamw_ref import (ACTIVITY, N_FLAT, N_SEG, SEG_LEN, Scaler, f32, hyper_dev, i32, spread_gradients,
+                               torch_adamw)
+from helpers.checks import DEV, check32  # (the f32 bar rule of the docstring: tests/helpers/checks.py)
+from helpers.checks import gen as _gen, ops as _ops
 
 pytestmark = pytest.mark.gpu
 
-F32_BAR = 1e-5
-
-
-def _ops():
-    from view_neti_amd import ops
-    return ops
-
-
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
-def rel(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / (b.norm() + 1e-300)).item()
-
-
-def check32(name, got, ref64, ref32, floor=F32_BAR):
-    e32 = rel(ref32, ref64)
-    bar = floor if 8 * e32 <= floor else 8 * e32
-    print(f"[{name}] e32={e32:.3e} kernel={rel(got.cpu(), ref64):.3e} bar={bar:.3e}")
-    check(name, got, ref64, bar)
-
-
-def f32(x):
-    return float(np.float32(x))
-
-
-def i32(*vals):
-    return torch.tensor(list(vals), dtype=torch.int32, device=DEV)
-
 
 # ------------------------------------------------------------------------------------------ AdamW
-B1, B2, ADAM_EPS = f32(0.9), f32(0.999), f32(1e-8)
-
-
-def hyper_dev(lr, wd, gdiv):
-    return torch.tensor([lr, B1, B2, ADAM_EPS, wd, gdiv], dtype=torch.float32, device=DEV)
-
-
-def torch_adamw(params, lr, wd):
-    return torch.optim.AdamW(params, lr=f32(lr), betas=(B1, B2), eps=ADAM_EPS, weight_decay=f32(wd))
-
-
-class Scaler:
-    """torch.cuda.amp.GradScaler.update(), restated: backoff 0.5 and a reset tracker on a non-finite step; else the tracker
-    counts and `growth_interval` clean steps in a row double the scale.  growth_interval <= 0: a static scale."""
-
-    def __init__(self, scale, growth_interval):
-        self.scale, self.tracker, self.interval, self.applied = float(scale), 0, growth_interval, 0
-
-    def update(self, found_inf):
-        if not found_inf:
-            self.applied += 1
-        if self.interval <= 0:
-            return
-        if found_inf:
-            self.scale *= 0.5
-            self.tracker = 0
-        else:
-            self.tracker += 1
-            if self.tracker >= self.interval:
-                self.scale *= 2.0
-                self.tracker = 0
-
-
-def spread_gradients(n, steps, seed):
-    """unscaled f32 gradients whose per-element magnitudes are spread over 2^-20 .. 2^4"""
-    g = _gen(seed)
-    mag = torch.exp2(torch.rand(n, generator=g) * 24 - 20)
-    return (torch.randn(steps, n, generator=g) * mag).float()
-
-
-N_FLAT = 8 * 1031 + 3  # a partly filled last block of 256, not a multiple of 4
-
-
 @pytest.mark.parametrize("gdiv", [1.0, 8.0])
 @pytest.mark.parametrize("wd", [0.0, 1e-2])
 @pytest.mark.parametrize("lr", [1e-3, 5e-2])
@@ -236,12 +165,6 @@ def test_adamw_flat_phases_over_two_buckets(clean):
         assert sc.cpu().tolist() == [16.0, 2.0, 0.0] and int(st.item()) == 6
     assert scaler.cpu().tolist() == [16.0, 2.0, 0.0] and int(step.item()) == 6
     assert not torch.equal(bk[0][0], state()[0][0]) and not torch.equal(bk[1][0], state()[1][0])
-
-
-SEG_LEN, N_SEG = 8 * 129 + 4, 5
-# segment ids with a gradient at each step, padded to n_active = 8 by repeating (the same segment several times in `active`).
-# segment 2: never; segment 1: once (step 2), then idle — it keeps decaying with a zero gradient and its own step count
-ACTIVITY = [[0], [0, 1], [0, 4], [0, 3], [3], [0, 4, 3], [0], [4], [0, 3], [0, 3, 4], [0], [0, 4]]
 
 
 def test_adamw_segments_against_torch():

@@ -3,7 +3,6 @@
 
 Every comparison is for BIT equality (torch.equal): a resumed run replays the same graphs on the same state with the same
 picks, so there is no tolerance to choose."""
-import random
 import shutil
 
 import numpy as np
@@ -11,66 +10,35 @@ import pytest
 import torch
 from PIL import Image
 
+from helpers.coach_runs import assert_end as _assert_end, coach as _coach, end_state as _end_state
+from helpers.coach_runs import mapper_tensors as _mapper_tensors, mode0_cfg as _mode0_cfg, toys as _toys
+from helpers.coach_runs import train_counting as _train
+from helpers.engines import FIELDS, build_device_rng_engine, feed_device_rng, run_steps, snapshot
+
 pytestmark = pytest.mark.gpu
 
 B, H, W, LR = 2, 64, 64, 3e-3
 ACCUM = 2
 SCENES = [0, 2, 0, 2]
 N_IMAGES = 4
-FIELDS = ("params", "exp_avg", "exp_avg_sq", "scaler", "rng_state", "opt_step", "seg_step", "hyper")
 
 
 # ------------------------------------------------------------------------------------------------ engine level
 def _build(mode3=False, cache=0):
-    """tests/test_dp_gpu.py::_build with everything that makes the state non-trivial switched on: device RNG, nested
-    dropout, accumulation 2, and a GradScaler that grows every 3 clean steps (mid-count after 2, doubling inside steps 3-4)"""
-    from view_neti_amd import sd_config as sc, synth
-    from view_neti_amd.engine.step import TrainStepEngine
-    from view_neti_amd.mapper import fourier_frequencies, init_mapper_state
-    cfg = sc.tiny()
-    D = cfg.clip.hidden_size
-    torch.manual_seed(0)
-    gen = torch.Generator().manual_seed(7)
-    mk = lambda: {k: v + 0.05 * torch.randn(v.shape, generator=gen) for k, v in init_mapper_state(64, 64, D).items()}
-    objs = [mk() for _ in range(3 if mode3 else 1)]
-    kw = {}
-    if mode3:
-        kw = dict(mapper_view=mk(), w_enc_view=fourier_frequencies([0.03, 2.0] + [0.5] * 12, 64, 0), norm_scale_view=0.35,
-                  alpha_view=0.3)
-    eng = TrainStepEngine(cfg, synth.unet_weights(cfg.unet), synth.vae_weights(cfg.vae), synth.clip_weights(cfg.clip), B,
-                          H, W, objs if mode3 else objs[0], fourier_frequencies([0.03, 2.0], 64, 0), 0.4, 0.2, lr=LR,
-                          grad_accum=ACCUM, device_rng=True, nested_dropout_prob=0.5, growth_interval=3, seed=5,
-                          moment_cache_images=cache, **kw)
-    return cfg, eng
+    """accumulation 2 on top of the device-RNG form: a GradScaler mid-count after 2 steps, doubling inside steps 3-4"""
+    return build_device_rng_engine(mode3, ACCUM, B, H, W, LR, moment_cache_images=cache)
 
 
 def _feed(cfg, eng, step, micro, mode3):
-    """micro-batch `micro` of optimizer step `step`: two of four fixed images (the pixels behind a dataset index never
-    change: what the moment cache relies on), captions and camera parameters that differ per micro-batch"""
-    from view_neti_amd import synth
-    k = ACCUM * step + micro
-    idx = [(2 * k) % N_IMAGES, (2 * k + 1) % N_IMAGES]
-    px = torch.cat([synth.gaussian((1, 3, H, W), 50 + i).clamp(-1, 1) for i in idx])
-    ph, phv = cfg.clip.vocab_size - 3, cfg.clip.vocab_size - 4
-    ids = synth.input_ids(B, ph, cfg.clip.vocab_size, view_placeholder_id=phv if mode3 else None)
-    kw = dict(image_idx=idx) if eng.n_cache else {}
-    if mode3:
-        eng.set_batch(px, ids, torch.full((B,), ph), torch.full((B,), phv), synth.gaussian((B, 12), 100 + k).clamp(-1, 1),
-                      object_index=SCENES[step], **kw)
-    else:
-        eng.set_batch(px, ids, torch.full((B,), ph), **kw)
+    feed_device_rng(cfg, eng, step, micro, mode3, scenes=SCENES, stride=ACCUM, n_images=N_IMAGES)
 
 
 def _steps(cfg, eng, steps, mode3):
-    for s in steps:
-        for m in range(ACCUM):
-            _feed(cfg, eng, s, m, mode3)
-            assert eng.step() is (m == ACCUM - 1)
+    run_steps(cfg, eng, steps, mode3, _feed)
 
 
 def _record(eng):
-    torch.cuda.synchronize()
-    rec = {f: getattr(eng, f).detach().cpu().clone() for f in FIELDS}
+    rec = snapshot(eng, FIELDS)
     rec["loss"] = eng.loss()
     return rec
 
@@ -176,72 +144,6 @@ def test_autotuner_picks_export_and_preload():
 
 
 # ------------------------------------------------------------------------------------------------ Coach
-def _toys(root):
-    root.mkdir(parents=True)
-    rng = np.random.RandomState(0)
-    for i in range(3):
-        Image.fromarray(rng.randint(0, 255, (90, 120, 3), dtype=np.uint8)).save(root / f"{i}.png")
-
-
-def _mode0_cfg(toys, out, *extra, max_steps=6):
-    """the tiny mode-0 configuration of test_coach_mode0_trains_and_saves: validation off, cosine schedule with warm-up,
-    nested dropout, accumulation 2, a checkpoint + trainer state every 3 steps"""
-    from view_neti_amd.compat import config as C
-    cfg = C.parse(C.RunConfig, [
-        "--data.train_data_dir", str(toys), "--data.placeholder_object_token", "<toy>", "--data.resolution", "64",
-        "--data.dataloader_num_workers", "0", "--data.augmentation_key", "5", "--model.word_embedding_dim", "128",
-        "--model.arch_view_net", "15", "--model.arch_view_disable_tl", "False", "--model.arch_mlp_hidden_dims", "64",
-        "--model.use_nested_dropout", "True", "--optim.max_train_steps", str(max_steps), "--optim.train_batch_size", "2",
-        "--optim.gradient_accumulation_steps", "2", "--optim.mixed_precision", "fp16", "--optim.lr_scheduler", "cosine",
-        "--optim.lr_warmup_steps", "2", "--log.save_steps", "3", "--log.save_trainer_state", "true",
-        "--eval.validation_steps", "1000", "--log.exp_dir", str(out), "--log.exp_name", "run", *extra])
-    cfg.log.exp_dir = cfg.log.exp_dir / cfg.log.exp_name
-    cfg.log.logging_dir = cfg.log.exp_dir / cfg.log.logging_dir
-    return cfg
-
-
-def _seed(s):
-    torch.manual_seed(s)
-    np.random.seed(s)
-    random.seed(s)
-
-
-def _coach(cfg, seed=0):
-    from view_neti_amd.compat.coach import Coach
-    _seed(seed)
-    return Coach(cfg)
-
-
-def _train(coach):
-    """-> number of optimizer steps train() performed"""
-    n, step = [0], coach.engine.step
-
-    def counting():
-        done = step()
-        n[0] += bool(done)
-        return done
-    coach.engine.step = counting
-    coach.train()
-    coach.engine.step = step
-    return n[0]
-
-
-def _end_state(coach):
-    torch.cuda.synchronize()
-    return {f: getattr(coach.engine, f).detach().cpu().clone() for f in FIELDS}
-
-
-def _assert_end(want, got):
-    for f in ("params", "exp_avg", "exp_avg_sq", "scaler", "rng_state", "seg_step", "opt_step"):
-        assert torch.equal(want[f], got[f]), f"{f} differs from the uninterrupted run"
-    assert want["hyper"][0] == got["hyper"][0]
-
-
-def _mapper_tensors(path):
-    ck = torch.load(path, map_location="cpu", weights_only=False)
-    return {(k, name): t for k, e in ck["mappers"].items() for name, t in e["state_dict"].items()}
-
-
 @pytest.fixture(scope="module")
 def run_a(tmp_path_factory):
     """the uninterrupted run: 6 optimizer steps, checkpoints and trainer states at 3 and 6"""

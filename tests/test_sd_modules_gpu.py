@@ -13,12 +13,12 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("cfg_name,with_view", [("tiny", False), ("tiny21", True)])
 def test_module_call_protocol_vae_scheduler_unet(cfg_name, with_view):
     from oracle import sd_ref as R
-    from test_step_gpu import build
+    from helpers.engines import build_train_engine as build
     from view_neti_amd import synth
     from view_neti_amd.compat.sd_modules import HipAutoencoderKL, HipDDPMScheduler, HipUNet2DConditionModel
     B, H, W = 2, 64, 64
     dev = "cuda"
-    cfg, eng, (uw, vw, cw), sd, w_enc, extra = build(cfg_name, B, H, W, with_view, device_rng=False, lr=1e-3)
+    cfg, eng, (uw, vw, cw), sd, w_enc, extra = build(cfg_name, B, H, W, with_view=with_view, device_rng=False, lr=1e-3)
     vae = HipAutoencoderKL(cfg.vae, vw, B, H, W)
     sched = HipDDPMScheduler(cfg.ddpm)
     unet = HipUNet2DConditionModel(cfg.unet, uw, B, H // 8, W // 8, cfg.clip.max_positions)

@@ -2,14 +2,11 @@
 relies on it to report is planted here by hand and must be reported — a stray store one element past a row end, one row
 past the last row and in the front guard, a logical element left unwritten — and a hardware NaN must not pass for the
 sentinel."""
-import os
-import sys
 
 import pytest
 import torch
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
-import slabs as S  # noqa: E402
+from helpers import slabs as S
 
 DTYPES = [torch.float16, torch.bfloat16, torch.float32]
 ROWS, COLS, GAP = 37, 40, 24

@@ -6,33 +6,9 @@ import math
 import pytest
 import torch
 
+from helpers.engines import build_train_engine as build  # (its defaults are this file's form: one object mapper, seed 1)
+
 pytestmark = pytest.mark.gpu
-
-
-def build(cfg_name, B, H, W, with_view=False, **kw):
-    from view_neti_amd import sd_config as sc, synth
-    from view_neti_amd.engine.step import TrainStepEngine
-    from view_neti_amd.mapper import fourier_frequencies, init_mapper_state
-    cfg = sc.CONFIGS[cfg_name]()
-    dev = "cuda"
-    gpu = not cfg_name.startswith("tiny")
-    uw = synth.unet_weights(cfg.unet, device=dev if gpu else "cpu")
-    vw = synth.vae_weights(cfg.vae, device=dev if gpu else "cpu")
-    cw = synth.clip_weights(cfg.clip, device=dev if gpu else "cpu")
-    D = cfg.clip.hidden_size
-    torch.manual_seed(0)
-    w_enc = fourier_frequencies([0.03, 2.0], 64, 0)
-    sd = init_mapper_state(64, 64, D)
-    gen = torch.Generator().manual_seed(1)
-    sd = {k: v + 0.05 * torch.randn(v.shape, generator=gen) for k, v in sd.items()}
-    extra = {}
-    if with_view:
-        w_enc_v = fourier_frequencies([0.03, 2.0] + [0.5] * 12, 64, 0)
-        sdv = init_mapper_state(64, 64, D)
-        sdv = {k: v + 0.05 * torch.randn(v.shape, generator=gen) for k, v in sdv.items()}
-        extra = dict(mapper_view=sdv, w_enc_view=w_enc_v, norm_scale_view=0.35, alpha_view=0.3)
-    eng = TrainStepEngine(cfg, uw, vw, cw, B, H, W, sd, w_enc, 0.4, 0.2, **extra, **kw)
-    return cfg, eng, (uw, vw, cw), sd, w_enc, extra
 
 
 # config 2 (mode 0, SD-1.5 family) / config 3 (mode 2: object + view mappers) / SD-2.1 family switches
@@ -46,7 +22,7 @@ def test_train_step_tiny_matches_oracle(cfg_name, with_view, H, W, unc):
     from view_neti_amd.engine.text import flatten_mapper_state
     B = 2
     lr = 4e-3
-    cfg, eng, (uw, vw, cw), sd, w_enc, extra = build(cfg_name, B, H, W, with_view, device_rng=False, lr=lr,
+    cfg, eng, (uw, vw, cw), sd, w_enc, extra = build(cfg_name, B, H, W, with_view=with_view, device_rng=False, lr=lr,
                                                      unconstrained_object=unc, unconstrained_view=unc)
     ph = cfg.clip.vocab_size - 3
     phv = cfg.clip.vocab_size - 4
@@ -245,7 +221,7 @@ def test_full_size_directional_derivative(cfg_name, B, H, W, with_view):
     mapper gradient produced by the hand-built backward must predict the change of the forward loss along its own
     direction: (L(p+e*d) - L(p-e*d)) / (2e) == g.d,  d = g/|g|.  A 10 % gradient-scale error fails."""
     from view_neti_amd import synth
-    cfg, eng, _, _, _, _ = build(cfg_name, B, H, W, with_view, device_rng=False, lr=1e-3)
+    cfg, eng, _, _, _, _ = build(cfg_name, B, H, W, with_view=with_view, device_rng=False, lr=1e-3)
     ph, phv = cfg.clip.vocab_size - 3, cfg.clip.vocab_size - 4
     ids = synth.input_ids(B, ph, cfg.clip.vocab_size, view_placeholder_id=phv if with_view else None)
     vparams = synth.gaussian((B, 12), 9).clamp(-1, 1) if with_view else None
@@ -313,7 +289,7 @@ def test_full_size_matches_oracle(cfg_name, B, H, W, with_view):
         if psutil.virtual_memory().available < 96 * 2 ** 30:
             pytest.skip("bs=4 fp32 autograd graph of the oracle needs ~60 GiB of host memory")
     torch.set_num_threads(min(32, len(os.sched_getaffinity(0))))
-    cfg, eng, (uw, vw, cw), sd, w_enc, extra = build(cfg_name, B, H, W, with_view, device_rng=False, lr=1e-3)
+    cfg, eng, (uw, vw, cw), sd, w_enc, extra = build(cfg_name, B, H, W, with_view=with_view, device_rng=False, lr=1e-3)
     ph, phv = cfg.clip.vocab_size - 3, cfg.clip.vocab_size - 4
     ids = synth.input_ids(B, ph, cfg.clip.vocab_size, view_placeholder_id=phv if with_view else None)
     px = synth.pixel_values(B, H, W)

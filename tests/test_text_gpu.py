@@ -5,12 +5,9 @@ import math
 import pytest
 import torch
 
+from helpers.checks import frob_rel as _rel
+
 pytestmark = pytest.mark.gpu
-
-
-def _rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / (b.norm() + 1e-20)).item()
 
 
 # (view mapper?, object bypass unconstrained?, view bypass unconstrained?, nested dropout?)

@@ -16,39 +16,17 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from test_kernels_gpu import DEV, DT, check, t16  # the kernel file's helpers (tests/ is on sys.path: rootdir imports)
+from helpers.checks import DEV, DT, F32_BAR, check, check32, t16
+from helpers.checks import gen as _gen, ops as _ops
 
 pytestmark = pytest.mark.gpu
 
-F32_BAR = 1e-5
 NAMES = ("net.0.weight", "net.0.bias", "net.1.weight", "net.1.bias", "net.3.weight", "net.3.bias", "net.4.weight",
          "net.4.bias", "output_layer.0.weight", "output_layer.0.bias")
 
 
-def _ops():
-    from view_neti_amd import ops
-    return ops
-
-
-def _gen(seed):
-    return torch.Generator().manual_seed(seed)
-
-
 def randn(*shape, seed, scale=1.0):
     return torch.randn(*shape, generator=_gen(seed)) * scale
-
-
-def rel(a, b):
-    a, b = a.double(), b.double()
-    return ((a - b).norm() / (b.norm() + 1e-300)).item()
-
-
-def check32(name, got, ref64, ref32, floor=F32_BAR):
-    """the f32 bar rule of the module docstring; prints e32, the kernel's error and the bar"""
-    e32 = rel(ref32, ref64)
-    bar = floor if 8 * e32 <= floor else 8 * e32
-    print(f"[{name}] e32={e32:.3e} kernel={rel(got.cpu(), ref64):.3e} bar={bar:.3e}")
-    check(name, got, ref64, bar)
 
 
 def dev(t):

@@ -11,69 +11,19 @@ import numpy as np
 import pytest
 import torch
 
-import test_resume_gpu as rt  # the tiny builders: _feed, _toys, _mode0_cfg, _coach, _train, _end_state, FIELDS
-from test_optim_rng_gpu import check32
+from helpers import coach_runs as rt  # toys, mode0_cfg, coach, train_counting, end_state, assert_end
+from helpers.checks import check32
+from helpers.engines import FORMS, STATE, build_device_rng_engine as _build, feed_six as _feed, run_steps
+from helpers.engines import six_steps as _six_steps  # (the cache of its runs is shared with tests/test_loss_options_gpu.py)
 
 pytestmark = pytest.mark.gpu
 
-B, H, W, LR = rt.B, rt.H, rt.W, rt.LR
-STATE = ("params", "exp_avg", "exp_avg_sq", "opt_step", "seg_step", "scaler", "rng_state")
-FORMS = {"one-mapper": (False, 1), "mode3": (True, 1), "accum2": (False, 2)}
+B, H, W, LR = 2, 64, 64, 3e-3
 ROWS = 16
 
 
-def _build(mode3=False, accum=1, **kw):
-    """tests/test_resume_gpu.py::_build with the accumulation and the f7 arguments open"""
-    from view_neti_amd import sd_config as sc, synth
-    from view_neti_amd.engine.step import TrainStepEngine
-    from view_neti_amd.mapper import fourier_frequencies, init_mapper_state
-    cfg = sc.tiny()
-    D = cfg.clip.hidden_size
-    torch.manual_seed(0)
-    gen = torch.Generator().manual_seed(7)
-    mk = lambda: {k: v + 0.05 * torch.randn(v.shape, generator=gen) for k, v in init_mapper_state(64, 64, D).items()}
-    objs = [mk() for _ in range(3 if mode3 else 1)]
-    if mode3:
-        kw = dict(kw, mapper_view=mk(), w_enc_view=fourier_frequencies([0.03, 2.0] + [0.5] * 12, 64, 0),
-                  norm_scale_view=0.35, alpha_view=0.3)
-    kw.setdefault("growth_interval", 3)
-    eng = TrainStepEngine(cfg, synth.unet_weights(cfg.unet), synth.vae_weights(cfg.vae), synth.clip_weights(cfg.clip), B,
-                          H, W, objs if mode3 else objs[0], fourier_frequencies([0.03, 2.0], 64, 0), 0.4, 0.2, lr=LR,
-                          grad_accum=accum, device_rng=True, nested_dropout_prob=0.5, seed=5, **kw)
-    return cfg, eng
-
-
-def _feed(cfg, eng, step, micro, mode3):
-    rt._feed(cfg, eng, step % len(rt.SCENES), micro, mode3)  # (its scene list has 4 entries: steps 4, 5 repeat 0, 1)
-
-
 def _steps(cfg, eng, steps, mode3):
-    for s in steps:
-        for m in range(eng.grad_accum):
-            _feed(cfg, eng, s, m, mode3)
-            assert eng.step() is (m == eng.grad_accum - 1)
-
-
-def _state(eng):
-    torch.cuda.synchronize()
-    return {f: getattr(eng, f).detach().cpu().clone() for f in STATE}
-
-
-_RUNS = {}
-
-
-def _six_steps(form, **kw):
-    """the state after 6 captured optimizer steps of an engine of this form; computed once per (form, arguments)"""
-    key = (form, tuple(sorted(kw.items())))
-    if key not in _RUNS:
-        mode3, accum = FORMS[form]
-        cfg, eng = _build(mode3, accum, **kw)
-        _feed(cfg, eng, 0, 0, mode3)
-        eng.capture()
-        _steps(cfg, eng, range(6), mode3)
-        rows = eng.read_telemetry() if eng.telemetry_rows else None
-        _RUNS[key] = (_state(eng), rows, eng.scaler.cpu().clone())
-    return _RUNS[key]
+    run_steps(cfg, eng, steps, mode3, _feed)
 
 
 @pytest.mark.parametrize("form", list(FORMS))
@@ -247,15 +197,15 @@ def _metrics(cfg):
 @pytest.fixture(scope="module")
 def toys(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("metrics")
-    rt._toys(tmp / "toys")
+    rt.toys(tmp / "toys")
     return tmp
 
 
 def _run6(toys, name, extra):
-    cfg = rt._mode0_cfg(toys / "toys", toys / name, "--log.train_metrics", "true", *extra)
-    coach = rt._coach(cfg)
-    assert rt._train(coach) == 6
-    return cfg, rt._end_state(coach), _metrics(cfg)
+    cfg = rt.mode0_cfg(toys / "toys", toys / name, "--log.train_metrics", "true", *extra)
+    coach = rt.coach(cfg)
+    assert rt.train_counting(coach) == 6
+    return cfg, rt.end_state(coach), _metrics(cfg)
 
 
 @pytest.fixture(scope="module")
@@ -280,18 +230,18 @@ def _check_lines(text, clipped):
 def _check_resume(toys, name, extra, cfg_a, end_a, text):
     """3 + 3: a run cut after step 3 and relaunched into the same directory continues the file byte for byte"""
     extra = ("--log.train_metrics", "true", *extra)
-    cfg = rt._mode0_cfg(toys / "toys", toys / name, "--log.auto_resume", "true", *extra)
-    coach = rt._coach(cfg)
+    cfg = rt.mode0_cfg(toys / "toys", toys / name, "--log.auto_resume", "true", *extra)
+    coach = rt.coach(cfg)
     cfg.optim.max_train_steps = 3
-    assert rt._train(coach) == 3
+    assert rt.train_counting(coach) == 3
     assert _metrics(cfg) == b"".join(l + b"\n" for l in text.splitlines()[:3])
     del coach
     with (cfg.log.exp_dir / "train-metrics.jsonl").open("a") as f:  # what a run killed after step 5 would have left behind
         f.write(json.dumps({"step": 4, "loss": 0.0}) + "\n" + json.dumps({"step": 5, "loss": 0.0}) + "\n")
-    cfg2 = rt._mode0_cfg(toys / "toys", toys / name, "--log.auto_resume", "true", *extra)
-    coach2 = rt._coach(cfg2, seed=77)
-    assert coach2.start_step == 3 and rt._train(coach2) == 3
-    rt._assert_end(end_a, rt._end_state(coach2))
+    cfg2 = rt.mode0_cfg(toys / "toys", toys / name, "--log.auto_resume", "true", *extra)
+    coach2 = rt.coach(cfg2, seed=77)
+    assert coach2.start_step == 3 and rt.train_counting(coach2) == 3
+    rt.assert_end(end_a, rt.end_state(coach2))
     assert _metrics(cfg2) == text, "the resumed run's record differs from the uninterrupted one"
 
 
@@ -300,7 +250,7 @@ def test_coach_record_is_deterministic_and_continues_across_a_resume(toys, run_u
     _check_lines(text, clipped=False)
     _, end_b, text_b = _run6(toys, "ub", ())
     assert text == text_b, "two runs of one configuration write different records"
-    rt._assert_end(end_a, end_b)
+    rt.assert_end(end_a, end_b)
     log = (cfg_a.log.logging_dir / "log.txt").read_text()
     assert "grad_norm" in log and "loss_scale" in log
     ck = torch.load(cfg_a.log.exp_dir / "mapper-steps-3_object.pt", map_location="cpu", weights_only=False)
@@ -308,10 +258,10 @@ def test_coach_record_is_deterministic_and_continues_across_a_resume(toys, run_u
     assert not any("max_grad_norm" in k or "train_metrics" in k for k in ck["vneti_ext"]["config_ext"])
     _check_resume(toys, "ur", (), cfg_a, end_a, text)
     # a state saved without clipping is refused by a clipped run, and the field is named
-    cfg3 = rt._mode0_cfg(toys / "toys", toys / "ux", "--model.mapper_checkpoint_path",
+    cfg3 = rt.mode0_cfg(toys / "toys", toys / "ux", "--model.mapper_checkpoint_path",
                          str(cfg_a.log.exp_dir / "mapper-steps-3"), "--optim.max_grad_norm", "0.05")
     with pytest.raises(ValueError, match="max_grad_norm"):
-        rt._coach(cfg3)
+        rt.coach(cfg3)
 
 
 def test_coach_clipped_run_resumes_and_is_told_apart(toys, run_u):
@@ -327,6 +277,6 @@ def test_coach_clipped_run_resumes_and_is_told_apart(toys, run_u):
     assert "max_grad_norm" not in ck["cfg"]["optim"] and ck["vneti_ext"]["config_ext"]["optim.max_grad_norm"] == float(bound)
     _check_resume(toys, "cr", clip, cfg_a, end_a, text)
     # and the reverse: a clipped run's state is refused by an unclipped run
-    cfg3 = rt._mode0_cfg(toys / "toys", toys / "cx", "--model.mapper_checkpoint_path", str(cfg_a.log.exp_dir / "mapper-steps-3"))
+    cfg3 = rt.mode0_cfg(toys / "toys", toys / "cx", "--model.mapper_checkpoint_path", str(cfg_a.log.exp_dir / "mapper-steps-3"))
     with pytest.raises(ValueError, match="max_grad_norm"):
-        rt._coach(cfg3)
+        rt.coach(cfg3)

@@ -6,12 +6,9 @@ import math
 import pytest
 import torch
 
+from helpers.checks import frob_rel as _rel
+
 pytestmark = pytest.mark.gpu
-
-
-def _rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / (b.norm() + 1e-20)).item()
 
 
 def _run(cfg_name, B, H, W, tol_pred, tol_grad):

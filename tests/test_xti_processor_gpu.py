@@ -32,6 +32,7 @@ class _Attn(torch.nn.Module):
         return mask
 
 
+# (not helpers.checks.frob_rel: this one also returns the largest element error and the reference's largest element)
 def _rel(a, b):
     a, b = a.float().cpu(), torch.as_tensor(b).float()
     return ((a - b).norm() / b.norm().clamp_min(1e-12)).item(), (a - b).abs().max().item(), b.abs().max().item()
