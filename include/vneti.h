@@ -461,6 +461,21 @@ int vneti_adamw_segments_clipped(float* p, const float* g, float* m, float* v, l
 #define VNETI_TELEMETRY_HEADER 10 /* then timesteps[Bn], losses[Bn] */
 int vneti_train_record(float* ring, int* count, int rows, int row_floats, int first_micro, const void* timesteps_i64,
                        const float* losses, int Bn, void* stream);
+/* Exponential moving average of the trained bucket on the device (extension: optim.ema_decay; DESIGN.md section 9, f9;
+ * diffusers' EMAModel, restated from the published code with inv_gamma 1 and min_decay 0).  Two launches in stream order.
+ * prepare (one thread) reads opt_step[0] (the step count of vneti_adamw_*) and ema_count = {n_updates, last_opt_step}:
+ * opt_step[0] == last_opt_step means the optimizer step was skipped on found_inf; then ema_coef = {unchanged, 0} and nothing
+ * else is written.  Otherwise k = n_updates + 1, s = max(0, k - update_after_step - 1), d = 0 when s == 0, else
+ * (1 + s) / (10 + s) when power == 0, else 1 - (1 + s)^(-power); d = min(d, max_decay), all in f64;
+ * ema_coef = {(float)(1 - d), d == 0 ? 2 : 1}, ema_count = {k, opt_step[0]}.
+ * apply (grid over n) by ema_coef[1]: 0 leaves ema untouched, 2 copies the bits of p, 1 is
+ * ema[i] = fmaf(ema_coef[0], p[i] - ema[i], ema[i]).  p is only read.  ema_hyper: device f32[4]
+ * {max_decay, update_after_step, power, 0}; ema_coef: device f32[2] scratch; ema_count: device int32[2].
+ * ema and p are 4-byte aligned, no more is assumed; they may not overlap.  64-bit addressing: no 2 GiB bound. */
+int vneti_ema_update(float* ema, const float* p, long long n, const int* opt_step, int* ema_count,
+                     const float* ema_hyper, float* ema_coef, void* stream);
+/* a[i] <-> b[i] for n floats, a bit copy both ways without a temporary; alignment and overlap rules of vneti_ema_update */
+int vneti_swap_f32(float* a, float* b, long long n, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * NeTI text path

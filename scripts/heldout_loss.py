@@ -3,7 +3,8 @@ runs during training, on `mapper-steps-N_{object,view}.pt` after the fact — sa
 engine for all iterations.
 
     python scripts/heldout_loss.py --input_dir <run> --iterations [1500,3000] \
-        [--heldout_loss_timesteps 4] [--heldout_loss_seed 0] [--eval_placeholder_object_tokens ["<scan65>"]]
+        [--heldout_loss_timesteps 4] [--heldout_loss_seed 0] [--eval_placeholder_object_tokens ["<scan65>"]] \
+        [--use_ema true]   (the averaged mappers mapper-ema-steps-N_* of a run with optim.ema_decay)
 
 Appends one line per iteration to <run>/heldout-loss-offline.jsonl and prints iteration x train / test.
 """
@@ -25,6 +26,7 @@ class HeldoutLossConfig:
     eval_placeholder_object_tokens: List[str] = field(default_factory=list)  # mode 3, as scripts/inference.py
     heldout_loss_timesteps: int = 4
     heldout_loss_seed: int = 0
+    use_ema: bool = False
 
 
 def main(args=None):
@@ -33,7 +35,7 @@ def main(args=None):
         raise SystemExit("heldout_loss: --input_dir and --iterations are required")
     from view_neti_amd.compat import heldout
     records = heldout.offline(cfg.input_dir, cfg.iterations, cfg.eval_placeholder_object_tokens,
-                              cfg.heldout_loss_timesteps, cfg.heldout_loss_seed)
+                              cfg.heldout_loss_timesteps, cfg.heldout_loss_seed, use_ema=cfg.use_ema)
     print(heldout.format_table(records))
     return records
 

@@ -5,7 +5,8 @@
     `inference_dir` as preds_object_{tok}_iter_{it}_seed{s}.png and results_all_iter_{it}_scans_{toks}_seeds_{seeds}.pt
 
     python scripts/inference.py --config_path input_configs/inference.yaml --input_dir <run> --iteration 1500 \
-        [--seeds [0,1]] [--batch 8] [--do_lpips true --lpips_vgg_weights A.pth --lpips_lin_weights B.pth]
+        [--seeds [0,1]] [--batch 8] [--do_lpips true --lpips_vgg_weights A.pth --lpips_lin_weights B.pth] \
+        [--use_ema true]   (the averaged mappers mapper-ema-steps-N_* of a run with optim.ema_decay; missing files raise)
 
   * free prompts x seeds -> PNG files:
 

@@ -66,6 +66,8 @@ class Coach:
         self.forward_only = forward_only
         self.rank, self.world, self.local_rank = parallel.world_info()
         self.device = device
+        if cfg.eval.validation_use_ema and cfg.optim.ema_decay is None:
+            raise ValueError("eval.validation_use_ema needs optim.ema_decay: this run keeps no average of the mappers")
         self._setup_logging()
         self._plan_resume()
         if cfg.optim.seed is not None:
@@ -131,6 +133,7 @@ class Coach:
             max_grad_norm=None if forward_only else cfg.optim.max_grad_norm,
             snr_gamma=None if forward_only else cfg.optim.snr_gamma,
             noise_offset=None if forward_only else cfg.optim.noise_offset,
+            **({} if forward_only else self._ema_kwargs()),
             telemetry_rows=self._telemetry_rows(), **first.engine_encoder_kwargs(), **kw)
         # per-step record (extension): every rank records (one launch list for all), rank 0 writes the file
         self.metrics = None
@@ -208,9 +211,11 @@ class Coach:
         stem = self._resume_dir / f"mapper-steps-{self.start_step}"
         sf = resume.state_file(self._resume_dir, self.start_step)
         if not sf.is_file():
+            ema = ("; the average of the mappers (optim.ema_decay) starts over from the loaded mappers with its counters at "
+                   "zero") if cfg.optim.ema_decay is not None else ""
             self.log(f"WARNING: warm start from {stem}: no {sf.name} beside it, so the AdamW moments and step counts are "
                      "zero, the loss scale is at its initial value and the RNG streams are fresh — the mappers, the step "
-                     "count and the learning-rate schedule continue, the run is NOT the one that was interrupted")
+                     f"count and the learning-rate schedule continue, the run is NOT the one that was interrupted{ema}")
             return
         if workers > 0:
             raise ValueError(f"resuming from {sf}: " + no_workers)
@@ -234,7 +239,12 @@ class Coach:
         return resume.fingerprint(cfg.learnable_mode, cfg.optim.train_batch_size, cfg.optim.gradient_accumulation_steps,
                                   self.world, cfg.optim.mixed_precision, cfg.seed, len(self.train_dataset), n_params,
                                   max_grad_norm=cfg.optim.max_grad_norm, snr_gamma=cfg.optim.snr_gamma,
-                                  noise_offset=cfg.optim.noise_offset)
+                                  noise_offset=cfg.optim.noise_offset, **self._ema_kwargs())
+
+    def _ema_kwargs(self) -> Dict:
+        """optim.ema_* as the training engine and the resume fingerprint take them"""
+        o = self.cfg.optim
+        return dict(ema_decay=o.ema_decay, ema_update_after_step=o.ema_update_after_step, ema_warmup_power=o.ema_warmup_power)
 
     def _telemetry_rows(self) -> int:
         """the ring holds twice the micro-steps between two reads (the loop reads it at every 50th optimizer step)"""
@@ -263,11 +273,12 @@ class Coach:
                        v_prediction=self.engine.cfg.ddpm.prediction_type == "v_prediction")
         self.metrics.append(lines_up_to(groups, global_step, omit_object=self.mapper_object_lookup is None, **snr))
 
-    def _load_resume_mappers(self, directory=None, step: Optional[int] = None):
+    def _load_resume_mappers(self, directory=None, step: Optional[int] = None, files=None):
         """the mappers this run TRAINS take their weights from the checkpoint pair (a frozen view mapper, modes 4 / 5,
         still comes from model.pretrained_view_mapper); flags such as the bypass alpha stay this run's"""
-        files = resume.mapper_files(self._resume_dir if directory is None else directory,
-                                    self.start_step if step is None else step, self.cfg.learnable_mode)
+        if files is None:
+            files = resume.mapper_files(self._resume_dir if directory is None else directory,
+                                        self.start_step if step is None else step, self.cfg.learnable_mode)
 
         def adopt(dst: NeTIMapper, src: NeTIMapper):
             dst.load_state_dict(src.mapper_state(), strict=False)  # (load_mapper has checked the key set)
@@ -287,14 +298,16 @@ class Coach:
                                                     cam_maxs=self.mapper_view.cam_maxs)
             adopt(self.mapper_view, view)
 
-    def load_mappers(self, directory, step: int):
+    def load_mappers(self, directory, step: int, ema: bool = False):
         """`mapper-steps-{step}` of `directory` into the modules and, IN PLACE, into the engine's bucket (the captured
-        graphs keep reading the same addresses) — the inverse of _sync_modules"""
+        graphs keep reading the same addresses) — the inverse of _sync_modules.  ema: the averaged mappers,
+        `mapper-ema-steps-{step}`, instead; a missing file raises, the raw ones are never taken in their place"""
         from ..engine.text import flatten_mapper_state
-        missing = [str(f) for f in resume.mapper_files(directory, step, self.cfg.learnable_mode).values() if not f.is_file()]
+        files = (resume.ema_mapper_files if ema else resume.mapper_files)(directory, step, self.cfg.learnable_mode)
+        missing = [str(f) for f in files.values() if not f.is_file()]
         if missing:
             raise FileNotFoundError(f"iteration {step}: missing {missing}")
-        self._load_resume_mappers(directory, step)
+        self._load_resume_mappers(directory, step, files)
         eng = self.engine
         for tid, k in self.object_slot.items():
             eng.object_params(k).copy_(flatten_mapper_state(self.mapper_object_lookup[tid].mapper_state()))
@@ -523,6 +536,19 @@ class Coach:
         self._sync_modules()
         self.checkpoint_handler.save_model(self.token_embedding, self.mapper_object_lookup, self.mapper_view,
                                            embeds_name, mapper_name)
+        if self.engine.ema is not None:
+            self._save_ema(mapper_name)
+
+    def _save_ema(self, mapper_name: str):
+        """`mapper-ema-*`: the averaged mappers through the same path and in the same format as the raw files, inside
+        ema_weights().  A frozen view mapper (modes 4 / 5) is not in the bucket and gets no file.  The modules hold the
+        raw weights again afterwards."""
+        eng = self.engine
+        trained_view = self.mapper_view if eng.view_params_flat().numel() > 0 else None
+        with eng.ema_weights():
+            self._sync_modules()
+            self.checkpoint_handler.save_mapper(self.mapper_object_lookup, trained_view, resume.ema_name(mapper_name))
+        self._sync_modules()
 
     def train(self):
         cfg, eng = self.cfg, self.engine
@@ -585,7 +611,11 @@ class Coach:
                                                      or global_step == cfg.optim.max_train_steps):
                         self.heldout.run(global_step)  # before the validation and the trainer-state save of this step
                     if self.validator is not None and global_step % cfg.eval.validation_steps == 0:  # coach.py:243,834
-                        self.validator.infer(global_step)
+                        if cfg.eval.validation_use_ema:  # the validator's engine reads the live bucket
+                            with eng.ema_weights():
+                                self.validator.infer(global_step)
+                        else:
+                            self.validator.infer(global_step)
                     if cfg.log.save_trainer_state and global_step % cfg.log.save_steps == 0:
                         self.save_trainer_state(global_step)  # after the mapper save AND the validation of this step
                 if global_step >= cfg.optim.max_train_steps:

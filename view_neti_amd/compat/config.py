@@ -188,6 +188,8 @@ class EvalConfig:
     # LPIPS(net="vgg") for that scoring (compat/lpips.py; fp16 runs only): torchvision's vgg16 and lpips' linear heads
     lpips_vgg_weights: Optional[Path] = field(default=None, metadata={"ext": True, "run_control": True})
     lpips_lin_weights: Optional[Path] = field(default=None, metadata={"ext": True, "run_control": True})
+    # run the validation (images, and validation_nvs) on the EMA of the mappers (optim.ema_decay)
+    validation_use_ema: bool = field(default=False, metadata={"ext": True, "run_control": True})
     # plain class attribute in the reference too (config.py:188)
     validation_view_tokens = None
 
@@ -227,8 +229,23 @@ class OptimConfig:
     # noise, noise += noise_offset * randn(B, C, 1, 1) (--noise_offset).  Held-out losses stay unweighted and offset-free.
     snr_gamma: Optional[float] = field(default=None, metadata={"ext": True, "when_set": True})
     noise_offset: Optional[float] = field(default=None, metadata={"ext": True, "when_set": True})
+    # extension: an exponential moving average of the mappers, kept on the device inside the captured step
+    # (diffusers' --use_ema / EMAModel with inv_gamma 1, min_decay 0).  ema_decay is the cap of the decay, in (0, 1);
+    # ema_update_after_step delays the averaging; ema_warmup_power None is the (1 + s) / (10 + s) ramp, a value > 0 the
+    # 1 - (1 + s)^(-power) one.  Same rules as max_grad_norm: they describe the trained model, named only where set
+    ema_decay: Optional[float] = field(default=None, metadata={"ext": True, "when_set": True})
+    ema_update_after_step: int = field(default=0, metadata={"ext": True, "when_set": True})
+    ema_warmup_power: Optional[float] = field(default=None, metadata={"ext": True, "when_set": True})
 
     def __post_init__(self):
+        if self.ema_decay is not None and not 0.0 < self.ema_decay < 1.0:
+            raise ValueError(f"optim.ema_decay must be in (0, 1) when set (is {self.ema_decay})")
+        if self.ema_warmup_power is not None and not 0.0 < self.ema_warmup_power < float("inf"):
+            raise ValueError(f"optim.ema_warmup_power must be > 0 and finite when set (is {self.ema_warmup_power})")
+        if self.ema_update_after_step < 0:
+            raise ValueError(f"optim.ema_update_after_step must be >= 0 (is {self.ema_update_after_step})")
+        if self.ema_decay is None and (self.ema_update_after_step or self.ema_warmup_power is not None):
+            raise ValueError("optim.ema_update_after_step / optim.ema_warmup_power need optim.ema_decay")
         for name in ("max_grad_norm", "snr_gamma", "noise_offset"):
             v = getattr(self, name)
             if v is not None and not v > 0:

@@ -100,16 +100,24 @@ def _mean(xs: Sequence[float]) -> Optional[float]:
     return float(sum(xs) / len(xs)) if len(xs) else None
 
 
-def make_record(step: int, p: Plan, losses: Dict[Optional[str], List[Tuple[Item, float]]]) -> dict:
-    """{"step", "timesteps", "objects": {tok: {"train", "test", "by_timestep": {t: {"train", "test"}}, "by_view": {cam: m}}}};
-    every m is a mean over per-sample losses, None for an empty split"""
-    objects = {}
-    for obj, rows in losses.items():
-        sel = lambda split, t=None: [v for it, v in rows if it.split == split and (t is None or it.timestep == t)]
-        objects[str(obj)] = {
-            "train": _mean(sel("train")), "test": _mean(sel("test")),
+def _object_record(p: Plan, rows: List[Tuple[Item, float]]) -> dict:
+    sel = lambda split, t=None: [v for it, v in rows if it.split == split and (t is None or it.timestep == t)]
+    return {"train": _mean(sel("train")), "test": _mean(sel("test")),
             "by_timestep": {str(t): {"train": _mean(sel("train", t)), "test": _mean(sel("test", t))} for t in p.timesteps},
             "by_view": {str(c): _mean([v for it, v in rows if it.cam == c]) for c in p.cams}}
+
+
+def make_record(step: int, p: Plan, losses: Dict[Optional[str], List[Tuple[Item, float]]],
+                ema_losses: Optional[Dict[Optional[str], List[Tuple[Item, float]]]] = None) -> dict:
+    """{"step", "timesteps", "objects": {tok: {"train", "test", "by_timestep": {t: {"train", "test"}}, "by_view": {cam: m}}}};
+    every m is a mean over per-sample losses, None for an empty split.  ema_losses (a run with optim.ema_decay): the same
+    plan evaluated with the averaged mappers; each object then gains "ema": {"train", "test", "by_timestep", "by_view"}
+    beside the unchanged raw fields"""
+    objects = {}
+    for obj, rows in losses.items():
+        objects[str(obj)] = _object_record(p, rows)
+        if ema_losses is not None:
+            objects[str(obj)]["ema"] = _object_record(p, ema_losses[obj])
     return {"step": int(step), "timesteps": list(p.timesteps), "objects": objects}
 
 
@@ -129,14 +137,18 @@ def read_records(path) -> List[dict]:
             for o in r["objects"].values():
                 o["by_timestep"] = {int(t): v for t, v in o["by_timestep"].items()}
                 o["by_view"] = {int(c): v for c, v in o["by_view"].items()}
+                if "ema" in o:
+                    o["ema"]["by_timestep"] = {int(t): v for t, v in o["ema"]["by_timestep"].items()}
+                    o["ema"]["by_view"] = {int(c): v for c, v in o["ema"]["by_view"].items()}
             out.append(r)
     return out
 
 
 def summary_line(step: int, record: dict) -> str:
     fmt = lambda v: "n/a" if v is None else f"{v:.5f}"
+    ema = lambda o: f" (ema: train {fmt(o['ema']['train'])} test {fmt(o['ema']['test'])})" if "ema" in o else ""
     return f"heldout loss step {step}: " + "  ".join(
-        f"{tok} train {fmt(o['train'])} test {fmt(o['test'])}" for tok, o in record["objects"].items())
+        f"{tok} train {fmt(o['train'])} test {fmt(o['test'])}{ema(o)}" for tok, o in record["objects"].items())
 
 
 # ---------------------------------------------------------------------------------------------- the evaluator
@@ -248,8 +260,17 @@ class HeldoutLoss:
             out[obj] = rows
         return out
 
-    def run(self, step: int, file_name: str = FILE_NAME) -> dict:
-        record = make_record(step, self.plan, self.evaluate())
+    def run(self, step: int, file_name: str = FILE_NAME, weights: Optional[str] = None) -> dict:
+        """one evaluation -> one line.  An engine that keeps an average of the mappers (optim.ema_decay) runs the plan twice,
+        raw and then inside ema_weights().  weights: a note of which saved weights the engine holds (offline, --use_ema)"""
+        losses, ema_losses = self.evaluate(), None
+        eng = self.coach.engine
+        if eng.ema is not None:
+            with eng.ema_weights():
+                ema_losses = self.evaluate()
+        record = make_record(step, self.plan, losses, ema_losses)
+        if weights is not None:
+            record["weights"] = weights
         append_record(Path(self.coach.cfg.log.exp_dir) / file_name, record)
         self.coach.log(summary_line(step, record))
         return record
@@ -257,10 +278,11 @@ class HeldoutLoss:
 
 # ---------------------------------------------------------------------------------------------- saved checkpoints
 def offline(input_dir, iterations: Sequence[int], eval_placeholder_object_tokens: Sequence[str] = (),
-            n_timesteps: int = 4, seed: int = 0, device: str = "cuda") -> List[dict]:
+            n_timesteps: int = 4, seed: int = 0, device: str = "cuda", use_ema: bool = False) -> List[dict]:
     """The same plan, seeds and inputs on the `mapper-steps-N` checkpoints of a finished run: the run's config from the
     first checkpoint (`inference_dtu.load_train_cfg`), ONE forward-only engine, each iteration's mappers copied into it
-    in place.  Appends to <input_dir>/heldout-loss-offline.jsonl and returns the records."""
+    in place.  Appends to <input_dir>/heldout-loss-offline.jsonl and returns the records.  use_ema: the averaged mappers
+    `mapper-ema-steps-N` of a run with optim.ema_decay instead (a missing file raises); such a line says "weights": "ema"."""
     from .coach import Coach
     from .inference_dtu import load_train_cfg
     input_dir = Path(input_dir)
@@ -275,8 +297,8 @@ def offline(input_dir, iterations: Sequence[int], eval_placeholder_object_tokens
     ev = HeldoutLoss(coach, n_timesteps=n_timesteps, seed=seed)
     records = []
     for it in iterations:
-        coach.load_mappers(input_dir, it)
-        records.append(ev.run(it, OFFLINE_FILE_NAME))
+        coach.load_mappers(input_dir, it, ema=use_ema)
+        records.append(ev.run(it, OFFLINE_FILE_NAME, weights="ema" if use_ema else None))
     return records
 
 

@@ -47,12 +47,15 @@ def load_inference(exp_dir, mapper_stem: str = "mapper-final", batch: int = 1, h
 
 def build_inference(cfg, exp_dir, mapper_stem: str, batch: int = 1, height: Optional[int] = None,
                     width: Optional[int] = None, object_token: Optional[str] = None, sampler: str = "dpm++2m",
-                    device: str = "cuda", per_sample: bool = False) -> Tuple[InferencePipeline, PromptManager]:
-    """load_inference with the run's config given (the reference's evaluation reads it from the view checkpoint)"""
+                    device: str = "cuda", per_sample: bool = False, view_stem: Optional[str] = None
+                    ) -> Tuple[InferencePipeline, PromptManager]:
+    """load_inference with the run's config given (the reference's evaluation reads it from the view checkpoint).
+    view_stem: the view mapper's file stem where it differs from the object mapper's (averaged object mapper beside a frozen
+    view mapper)"""
     exp_dir = Path(exp_dir)
     sd = _sd_family(cfg)
     tok = load_tokenizer(str(cfg.model.pretrained_model_name_or_path), sd.clip.vocab_size)
-    obj_path, view_path = exp_dir / f"{mapper_stem}_object.pt", exp_dir / f"{mapper_stem}_view.pt"
+    obj_path, view_path = exp_dir / f"{mapper_stem}_object.pt", exp_dir / f"{view_stem or mapper_stem}_view.pt"
     if obj_path.exists():
         raw = torch.load(obj_path, map_location="cpu", weights_only=False)
         object_tokens = [e["placeholder_object_token"] for e in raw["mappers"].values()]

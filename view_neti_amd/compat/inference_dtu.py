@@ -44,6 +44,8 @@ class InferenceConfig:
     do_lpips: bool = False
     lpips_vgg_weights: Optional[Path] = None
     lpips_lin_weights: Optional[Path] = None
+    # evaluate the averaged mappers mapper-ema-steps-N_* of a run with optim.ema_decay instead of the raw ones
+    use_ema: bool = False
 
     def __post_init__(self):
         if self.do_lpips and (self.lpips_vgg_weights is None or self.lpips_lin_weights is None):
@@ -145,13 +147,31 @@ def generate_views(pipe, pm, objects: Sequence[str], cam_idxs: Sequence[int], se
     return {o: {c: np.stack([imgs[(o, c, s)] for s in seeds]) for c in cam_idxs} for o in objects}
 
 
-def load_nvs_pipeline(train_cfg, step: int, batch: int, device: str = "cuda"):
+def nvs_mapper_stems(input_dir, step: int, learnable_mode: int, use_ema: bool = False) -> Tuple[str, str]:
+    """(object stem, view stem) of the checkpoint files the evaluation of iteration `step` loads.  use_ema: the averaged
+    mappers `mapper-ema-steps-N_*` for every mapper the run trained — a missing one raises naming it, the raw file is never
+    taken in its place; a frozen view mapper (modes 4 / 5) has no average and stays the raw file"""
+    from . import resume
+    raw = f"mapper-steps-{step}"
+    if not use_ema:
+        return raw, raw
+    files = resume.ema_mapper_files(input_dir, step, learnable_mode)
+    missing = [str(f) for f in files.values() if not f.is_file()]
+    if missing:
+        raise FileNotFoundError(f"use_ema: iteration {step} has no averaged mappers: missing {missing} (they are written "
+                                "by runs with optim.ema_decay)")
+    ema = resume.ema_name(raw)
+    return (ema if "object" in files else raw), (ema if "view" in files else raw)
+
+
+def load_nvs_pipeline(train_cfg, step: int, batch: int, device: str = "cuda", use_ema: bool = False):
     """the run's mappers at `step` (mapper-steps-{step}_{view,object}.pt, inference_dtu.py:119-123), every object
     mapper in one per-sample bucket, at the novel-view resolution"""
     from .inference import build_inference
     h, w = nvs_resolution(train_cfg, _sd_family(train_cfg))
-    return build_inference(train_cfg, Path(train_cfg.log.exp_dir), f"mapper-steps-{step}", batch, h, w,
-                           device=device, per_sample=True)
+    exp_dir = Path(train_cfg.log.exp_dir)
+    obj_stem, view_stem = nvs_mapper_stems(exp_dir, step, train_cfg.learnable_mode, use_ema)
+    return build_inference(train_cfg, exp_dir, obj_stem, batch, h, w, device=device, per_sample=True, view_stem=view_stem)
 
 
 def dtu_generate_camidxs_to_preds(train_cfg, cam_idxs, step, num_denoising_steps: int = 30,
@@ -216,7 +236,7 @@ def run(icfg: InferenceConfig) -> Dict[Optional[str], dict]:
         raise NotImplementedError("inference.py script only implemented for dtu dataset")
     if icfg.eval_placeholder_object_tokens:
         train_cfg.eval.eval_placeholder_object_tokens = list(icfg.eval_placeholder_object_tokens)
-    pipe, pm = load_nvs_pipeline(train_cfg, icfg.iteration, icfg.batch)
+    pipe, pm = load_nvs_pipeline(train_cfg, icfg.iteration, icfg.batch, use_ema=icfg.use_ema)
     tokens = pipe.object_tokens
     if train_cfg.learnable_mode == 3:
         evals = list(train_cfg.eval.eval_placeholder_object_tokens or tokens[:1])

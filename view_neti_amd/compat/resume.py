@@ -147,6 +147,19 @@ def mapper_files(directory, step: int, learnable_mode: int) -> Dict[str, Path]:
     return out
 
 
+def ema_name(name: str) -> str:
+    """the name under which the EMA of the mappers is saved beside `mapper-*`: mapper-steps-N.pt ->
+    mapper-ema-steps-N.pt, mapper-final.pt -> mapper-ema-final.pt, with or without the _object / _view ending"""
+    if not name.startswith("mapper-") or name.startswith("mapper-ema-"):
+        raise ValueError(f"'{name}' is not the name of a raw mapper checkpoint")
+    return "mapper-ema-" + name[len("mapper-"):]
+
+
+def ema_mapper_files(directory, step: int, learnable_mode: int) -> Dict[str, Path]:
+    """`mapper_files` of the averaged mappers; a frozen view mapper (modes 4 / 5) is not in the bucket and has none"""
+    return {k: f.with_name(ema_name(f.name)) for k, f in mapper_files(directory, step, learnable_mode).items()}
+
+
 def state_file(directory, step: int, rank: int = 0) -> Path:
     name = f"trainer-state-steps-{step}.pt" if rank == 0 else f"trainer-state-steps-{step}.host-rank{rank}.pt"
     return Path(directory) / name
@@ -236,7 +249,8 @@ def prune_states(directory, keep: int) -> List[Path]:
 # ---------------------------------------------------------------------------------------------- fingerprint
 def fingerprint(learnable_mode: int, batch_size: int, grad_accum: int, world: int, precision: str, seed: Optional[int],
                 dataset_len: int, n_params: Optional[int] = None, max_grad_norm: Optional[float] = None,
-                snr_gamma: Optional[float] = None, noise_offset: Optional[float] = None) -> Dict[str, Any]:
+                snr_gamma: Optional[float] = None, noise_offset: Optional[float] = None, ema_decay: Optional[float] = None,
+                ema_update_after_step: int = 0, ema_warmup_power: Optional[float] = None) -> Dict[str, Any]:
     fp = {"learnable_mode": int(learnable_mode), "train_batch_size": int(batch_size),
           "gradient_accumulation_steps": int(grad_accum), "world_size": int(world), "precision": str(precision),
           "seed": -1 if seed is None else int(seed), "dataset_len": int(dataset_len)}
@@ -248,11 +262,17 @@ def fingerprint(learnable_mode: int, batch_size: int, grad_accum: int, world: in
         fp["snr_gamma"] = float(snr_gamma)
     if noise_offset is not None:
         fp["noise_offset"] = float(noise_offset)
+    if ema_decay is not None:  # (and for the average of the mappers)
+        fp["ema_decay"] = float(ema_decay)
+    if ema_update_after_step:
+        fp["ema_update_after_step"] = int(ema_update_after_step)
+    if ema_warmup_power is not None:
+        fp["ema_warmup_power"] = float(ema_warmup_power)
     return fp
 
 
 # fields that are present only where they are set: absent on one side and present on the other is a difference too
-_WHEN_SET = ("max_grad_norm", "snr_gamma", "noise_offset")
+_WHEN_SET = ("max_grad_norm", "snr_gamma", "noise_offset", "ema_decay", "ema_update_after_step", "ema_warmup_power")
 
 
 def check_fingerprint(saved: Dict[str, Any], current: Dict[str, Any]):

@@ -1109,3 +1109,130 @@ extern "C" int vneti_train_record(float* ring, int* count, int rows, int row_flo
                      (const long long*)timesteps_i64, losses, Bn);
   return vneti_check_launch("train_record");
 }
+
+// ---- exponential moving average of the trained bucket (extension: optim.ema_decay) --------------
+// Two launches in stream order, the idiom of adamw_flat_launch with scaler_update_kernel.  prepare (one thread) decides from
+// device scalars whether the optimizer step before it was applied (`opt_step` advances on applied steps only,
+// scaler_update_kernel) and, if so, this update's decay: diffusers' EMAModel.get_decay with inv_gamma 1 and min_decay 0,
+// restated from the published code, in f64.  coef = {one_minus_decay, apply}: apply 0 = nothing to do (skipped step),
+// 1 = the update, 2 = decay exactly 0, a bit copy (e + 1 * (p - e) is not p in f32).
+__global__ void ema_prepare_kernel(const int* opt_step, int* count, const float* hyper, float* coef) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const int cur = opt_step[0];
+  if (cur == count[1]) {  // skipped on found_inf: neither the count nor the average moves
+    coef[1] = 0.f;
+    return;
+  }
+  const long long k = (long long)count[0] + 1;
+  const long long after = (long long)hyper[1];
+  const long long s = k - after - 1 > 0 ? k - after - 1 : 0;
+  const double max_decay = (double)hyper[0], power = (double)hyper[2];
+  double d = 0.0;
+  if (s > 0) d = power == 0.0 ? (1.0 + (double)s) / (10.0 + (double)s) : 1.0 - pow(1.0 + (double)s, -power);
+  d = fmin(d, max_decay);
+  d = fmax(d, 0.0);
+  coef[0] = (float)(1.0 - d);
+  coef[1] = d == 0.0 ? 2.f : 1.f;
+  count[0] = (int)k;
+  count[1] = cur;
+}
+// The flat ranges are split at the FIRST operand's 16-byte boundaries into a head of 0..3 floats, 16-byte vectors and a tail
+// of 0..3 floats; the second operand's vectors are loaded (stored) as one 16-byte access when it happens to share that
+// alignment and as four dwords when it does not (a uniform branch).  Nothing but 4-byte alignment is assumed of either.
+// Plain 64-bit pointers: no buffer resource, no 2 GiB bound.  Thread gid owns vector gid; threads 0..2 also own the edges.
+struct FlatSplit {
+  long long head, nvec, tail;
+};
+__device__ __forceinline__ FlatSplit flat_split(const void* first, long long n) {
+  FlatSplit s;
+  s.head = (long long)(((16u - (unsigned)((uintptr_t)first & 15u)) & 15u) >> 2);
+  if (s.head > n) s.head = n;
+  s.nvec = (n - s.head) >> 2;
+  s.tail = n - s.head - 4 * s.nvec;
+  return s;
+}
+__device__ __forceinline__ uint4 ld4_u32(const uint32_t* q, bool aligned) {
+  if (aligned) return *reinterpret_cast<const uint4*>(q);
+  return make_uint4(q[0], q[1], q[2], q[3]);
+}
+__device__ __forceinline__ void st4_u32(uint32_t* q, uint4 v, bool aligned) {
+  if (aligned) {
+    *reinterpret_cast<uint4*>(q) = v;
+  } else {
+    q[0] = v.x, q[1] = v.y, q[2] = v.z, q[3] = v.w;
+  }
+}
+__device__ __forceinline__ uint32_t ema_one(uint32_t e, uint32_t q, float c, bool copy) {
+  if (copy) return q;  // the bits of p: NaN payloads and -0.0 included
+  const float ef = __uint_as_float(e), qf = __uint_as_float(q);
+  return __float_as_uint(fmaf(c, qf - ef, ef));  // diffusers: s_param.sub_(one_minus_decay * (s_param - param))
+}
+__global__ __launch_bounds__(256) void ema_apply_kernel(uint32_t* __restrict__ ema, const uint32_t* __restrict__ p,
+                                                        long long n, const float* __restrict__ coef) {
+  const float mode = coef[1];
+  if (mode == 0.f) return;
+  const float c = coef[0];
+  const bool copy = mode == 2.f;
+  const FlatSplit sp = flat_split(ema, n);
+  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (gid < sp.nvec) {
+    const long long i = sp.head + 4 * gid;
+    const bool p_al = ((uintptr_t)(p + sp.head) & 15u) == 0;
+    const uint4 e = *reinterpret_cast<const uint4*>(ema + i);
+    const uint4 q = ld4_u32(p + i, p_al);
+    *reinterpret_cast<uint4*>(ema + i) = make_uint4(ema_one(e.x, q.x, c, copy), ema_one(e.y, q.y, c, copy),
+                                                    ema_one(e.z, q.z, c, copy), ema_one(e.w, q.w, c, copy));
+  }
+  if (gid < sp.head) ema[gid] = ema_one(ema[gid], p[gid], c, copy);
+  if (gid < sp.tail) {
+    const long long i = sp.head + 4 * sp.nvec + gid;
+    ema[i] = ema_one(ema[i], p[i], c, copy);
+  }
+}
+// a[i] <-> b[i], bit for bit, each element read and written by one thread: no temporary
+__global__ __launch_bounds__(256) void swap_u32_kernel(uint32_t* __restrict__ a, uint32_t* __restrict__ b, long long n) {
+  const FlatSplit sp = flat_split(a, n);
+  const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (gid < sp.nvec) {
+    const long long i = sp.head + 4 * gid;
+    const bool b_al = ((uintptr_t)(b + sp.head) & 15u) == 0;
+    const uint4 x = *reinterpret_cast<const uint4*>(a + i);
+    const uint4 y = ld4_u32(b + i, b_al);
+    *reinterpret_cast<uint4*>(a + i) = y;
+    st4_u32(b + i, x, b_al);
+  }
+  if (gid < sp.head) {
+    const uint32_t x = a[gid];
+    a[gid] = b[gid];
+    b[gid] = x;
+  }
+  if (gid < sp.tail) {
+    const long long i = sp.head + 4 * sp.nvec + gid;
+    const uint32_t x = a[i];
+    a[i] = b[i];
+    b[i] = x;
+  }
+}
+// blocks of 256 threads, one per 16-byte vector of a range of n floats at any alignment (at least one: the edges)
+static inline long long flat_blocks(long long n) { return cdivl(n / 4 + 1, 256); }
+
+extern "C" int vneti_ema_update(float* ema, const float* p, long long n, const int* opt_step, int* ema_count,
+                                const float* ema_hyper, float* ema_coef, void* stream) {
+  VN_REQUIRE(ema && p && opt_step && ema_count && ema_hyper && ema_coef && n > 0, "ema_update: bad arguments");
+  VN_REQUIRE((((uintptr_t)ema | (uintptr_t)p) & 3u) == 0, "ema_update: ema and p must be 4-byte aligned");
+  VN_REQUIRE(ema + n <= p || p + n <= ema, "ema_update: ema and p overlap");
+  VN_REQUIRE(flat_blocks(n) <= 0x7fffffffLL, "ema_update: %lld floats is more than one launch covers", n);
+  hipLaunchKernelGGL(ema_prepare_kernel, dim3(1), dim3(64), 0, ST, opt_step, ema_count, ema_hyper, ema_coef);
+  hipLaunchKernelGGL(ema_apply_kernel, dim3((unsigned)flat_blocks(n)), dim3(256), 0, ST, (uint32_t*)ema,
+                     (const uint32_t*)p, n, (const float*)ema_coef);
+  return vneti_check_launch("ema_update");
+}
+
+extern "C" int vneti_swap_f32(float* a, float* b, long long n, void* stream) {
+  VN_REQUIRE(a && b && n > 0, "swap_f32: bad arguments");
+  VN_REQUIRE((((uintptr_t)a | (uintptr_t)b) & 3u) == 0, "swap_f32: a and b must be 4-byte aligned");
+  VN_REQUIRE(a + n <= b || b + n <= a, "swap_f32: the ranges overlap");
+  VN_REQUIRE(flat_blocks(n) <= 0x7fffffffLL, "swap_f32: %lld floats is more than one launch covers", n);
+  hipLaunchKernelGGL(swap_u32_kernel, dim3((unsigned)flat_blocks(n)), dim3(256), 0, ST, (uint32_t*)a, (uint32_t*)b, n);
+  return vneti_check_launch("swap_f32");
+}

@@ -54,7 +54,9 @@ class TrainStepEngine:
                  legacy_pe_object: Optional[torch.Tensor] = None, enc_dim_object: int = 64,
                  output_bypass_object: bool = True, output_bypass_view: bool = True, exchange=None,
                  moment_cache_images: int = 0, max_grad_norm: Optional[float] = None, telemetry_rows: int = 0,
-                 snr_gamma: Optional[float] = None, noise_offset: Optional[float] = None):
+                 snr_gamma: Optional[float] = None, noise_offset: Optional[float] = None,
+                 ema_decay: Optional[float] = None, ema_update_after_step: int = 0,
+                 ema_warmup_power: Optional[float] = None):
         """mapper_object: one mapper state_dict, or a list of them (learnable_mode 3: one object mapper per
         scene, `mapper_object_lookup`, training/coach.py:505-552) — `set_batch(object_index=k)` picks the one
         the batch trains.
@@ -65,8 +67,23 @@ class TrainStepEngine:
         snr_gamma: Min-SNR-gamma weighting of the training loss (diffusers' --snr_gamma; inf is legal: every weight 1).
         noise_offset: offset noise, noise += noise_offset * randn(B, C, 1, 1) (diffusers' --noise_offset).  Both are None
         or > 0 and touch the TRAINING objective only: eval_losses() stays the plain MSE on plain noise, and the ring's
-        per-sample losses stay unweighted.  Both off: the step enqueues the launches it always did."""
+        per-sample losses stay unweighted.  Both off: the step enqueues the launches it always did.
+        ema_decay: keep an exponential moving average of the bucket on the device, updated at the end of every applied
+        optimizer step (diffusers' EMAModel; None or the cap of the decay, in (0, 1)).  ema_update_after_step delays it,
+        ema_warmup_power (None or > 0) picks the 1 - (1 + s)^(-power) ramp over (1 + s) / (10 + s).  The average only reads
+        `params`; ema_weights() swaps it in for evaluation.  Off: no buffer, no launch."""
         from .text import flatten_mapper_state
+        # the average's settings (DESIGN §9, f9), refused before anything is built.  (`not a < x < b` also refuses nan)
+        if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay must be in (0, 1) (is {ema_decay!r}); None turns the average off")
+        if ema_warmup_power is not None and not 0.0 < float(ema_warmup_power) < float("inf"):
+            raise ValueError(f"ema_warmup_power must be > 0 and finite (is {ema_warmup_power!r}); None is the (1+s)/(10+s) ramp")
+        if int(ema_update_after_step) != ema_update_after_step or not 0 <= ema_update_after_step < 2 ** 24:
+            raise ValueError(f"ema_update_after_step must be an integer in [0, 2^24) (is {ema_update_after_step!r})")
+        if ema_decay is None and (ema_update_after_step or ema_warmup_power is not None):
+            raise ValueError("ema_update_after_step / ema_warmup_power need ema_decay")
+        if ema_decay is not None and not need_backward:
+            raise ValueError("ema_decay needs an engine that trains")
         self.cfg = cfg
         self.B, self.H, self.W = batch, height, width
         self.dev = device
@@ -244,6 +261,20 @@ class TrainStepEngine:
         if self.noise_offset is not None:
             self.offset_noise = torch.zeros(batch, Lc, dtype=torch.float32, device=device)
             self._offset_noise_set = False  # host-supplied randomness: has set_noise() delivered the draw
+        # ---- the average of the bucket (settings checked above).  `ema` and `ema_count` ARE trainer state;
+        # ema_coef is scratch
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_update_after_step = int(ema_update_after_step) or None  # (None where unset: the _WHEN_SET rule)
+        self.ema_warmup_power = None if ema_warmup_power is None else float(ema_warmup_power)
+        self.ema = self.ema_count = None
+        self._ema_swapped = False  # inside ema_weights(): `params` holds the average
+        if self.ema_decay is not None:
+            self.ema = self.params.clone()
+            self.ema_count = torch.zeros(2, dtype=torch.int32, device=device)  # {n_updates, last_opt_step}
+            self.ema_hyper = torch.tensor([self.ema_decay, float(int(ema_update_after_step)), self.ema_warmup_power or 0.0,
+                                           0.0], dtype=torch.float32, device=device)
+            self.ema_coef = torch.zeros(ops.EMA_COEF_FLOATS, dtype=torch.float32, device=device)
+            self._STATE = type(self)._STATE + ("ema", "ema_count")  # (this instance's: a state without EMA has neither)
 
     # ------------------------------------------------------------------ inputs
     def set_batch(self, pixel_values, input_ids, placeholder_object, placeholder_view=None, view_params=None,
@@ -322,7 +353,8 @@ class TrainStepEngine:
     # ------------------------------------------------------------------ trainer state (resumable training)
     _STATE = ("params", "exp_avg", "exp_avg_sq", "opt_step", "seg_step", "scaler", "rng_state", "hyper")
 
-    _WHEN_SET = ("max_grad_norm", "snr_gamma", "noise_offset")  # described only where set: older states read as "unset"
+    # described only where set: older states read as "unset"
+    _WHEN_SET = ("max_grad_norm", "snr_gamma", "noise_offset", "ema_decay", "ema_update_after_step", "ema_warmup_power")
 
     def _describe(self) -> Dict:
         from .. import lib
@@ -336,6 +368,7 @@ class TrainStepEngine:
         warm-up, plus the hyper-parameters — and a description `load_state_dict` validates.  Gradients are not state: the
         first micro-step of a group overwrites them.  The VAE moment cache is not state either (D14: a hit and a miss are
         bit-identical)."""
+        self._refuse_ema_weights("state_dict()")
         if self.micro != 0:
             raise RuntimeError(f"state_dict() inside a gradient-accumulation group (micro-step {self.micro} of "
                                f"{self.grad_accum}): the accumulated gradients are not part of the state")
@@ -347,11 +380,12 @@ class TrainStepEngine:
         """copies IN PLACE (the captured graphs hold these buffers' addresses): valid before capture() — whose warm-up
         snapshot then carries the loaded values — and after it, without re-capture.  `hyper` comes back as saved, lr
         included; a caller with a schedule rewrites the lr through set_lr()."""
+        self._refuse_ema_weights("load_state_dict()")
         if self.micro != 0:
             raise RuntimeError("load_state_dict() inside a gradient-accumulation group")
         want, have = self._describe(), sd.get("meta", {})
         bad = [f"{k}: saved {have.get(k)!r}, this engine {v!r}" for k, v in want.items() if have.get(k) != v]
-        # (a state from before f7 / f8 has no such keys: unclipped, unweighted, no offset noise)
+        # (a state from before f7 / f8 / f9 has no such keys: unclipped, unweighted, no offset noise, no average)
         bad += [f"{k}: saved {have[k]!r}, this engine None" for k in self._WHEN_SET if k in have and k not in want]
         bad += [f"{name}: saved shape {tuple(sd[name].shape) if name in sd else None}, this engine "
                 f"{tuple(getattr(self, name).shape)}" for name in self._STATE
@@ -366,6 +400,7 @@ class TrainStepEngine:
     def forward_backward(self, accumulate: bool = False, cached: bool = False):
         """cached: the batch's VAE moments come out of the moment cache (no encoder launches); otherwise the encoder runs
         and, with a cache, its moments are stored at the batch's image slots."""
+        self._refuse_ema_weights("forward_backward()")
         B, Lc, hw = self.B, self.cfg.vae.latent_channels, self.h * self.w
         self.text.accumulate_grads = accumulate
         if self.device_rng:
@@ -444,6 +479,14 @@ class TrainStepEngine:
                              ops.telemetry_row_floats(self.B) if self.telemetry_rows else 0)
 
     def optimizer_step(self):
+        self._refuse_ema_weights("optimizer_step()")
+        self._adamw()
+        if self.ema is not None:
+            # after the call that carried OPT_FINISH: opt_step has advanced iff the step was applied.  One flat launch over
+            # the whole bucket, one count (EMAModel over all parameters); a mapper that never trained has p == ema exactly
+            ops.ema_update(self.ema, self.params, self.opt_step, self.ema_count, self.ema_hyper, self.ema_coef)
+
+    def _adamw(self):
         a = (self.hyper, self.scaler, self.opt_step)
         kw = dict(growth_interval=self.growth_interval)
         flat, segments = ops.adamw_flat, ops.adamw_segments
@@ -468,6 +511,36 @@ class TrainStepEngine:
         if has_view:
             flat(*view, *a, phases=ops.OPT_APPLY, **kw)
         segments(*obj, *a, phases=ops.OPT_APPLY | ops.OPT_FINISH, **kw)
+
+    # ------------------------------------------------------------------ the averaged mappers
+    def _refuse_ema_weights(self, what: str):
+        if self._ema_swapped:
+            raise RuntimeError(f"{what} inside ema_weights(): `params` holds the average; leave the context first")
+
+    def ema_weights(self):
+        """context manager: `params` holds the EMA (and `ema` the raw weights) while it is open — one swap_f32 launch on
+        enter, one on exit, both bit copies — so eval_losses(), an InferenceEngine over the live bucket and mapper saving
+        see the average through the code path they always use.  Legal between optimizer steps only; training, capture and
+        the state calls raise inside it."""
+        from contextlib import contextmanager
+        if self.ema is None:
+            raise RuntimeError("ema_weights(): this engine was built without ema_decay")
+        self._refuse_ema_weights("ema_weights()")
+        if self.micro != 0:
+            raise RuntimeError(f"ema_weights() inside a gradient-accumulation group (micro-step {self.micro} of "
+                               f"{self.grad_accum}): legal between optimizer steps only")
+
+        @contextmanager
+        def swapped():
+            ops.swap_f32(self.params, self.ema)
+            self._ema_swapped = True
+            try:
+                yield self
+            finally:
+                ops.swap_f32(self.params, self.ema)
+                self._ema_swapped = False
+
+        return swapped()
 
     # ------------------------------------------------------------------ per-step record (DESIGN §9, f7)
     def read_telemetry(self):
@@ -566,6 +639,7 @@ class TrainStepEngine:
 
     def step_eager(self):
         """one micro-step; the optimizer runs after every `grad_accum`-th micro-step."""
+        self._refuse_ema_weights("step()")
         self._refuse_eval_batch()
         cached = self._use_cache()
         self.forward_backward(accumulate=self.micro > 0, cached=cached)
@@ -585,6 +659,7 @@ class TrainStepEngine:
         Fallbacks keep the older shape [forward+backward] -> host-issued all-reduce -> [optimizer]: the gloo backend,
         several object mappers (host-dependent exchange plan), and a communicator that refuses capture."""
         import os
+        self._refuse_ema_weights("capture()")
         want = self._exchange_capturable()
         err = None
         try:
@@ -615,7 +690,7 @@ class TrainStepEngine:
         # capture raises (the fallback re-captures from the same state, not from one optimizer step later)
         # (and the record's ring, its counter and the norm outputs: the warm-up must leave no rows behind)
         saved = (self.params, self.exp_avg, self.exp_avg_sq, self.opt_step, self.scaler, self.rng_state, self.seg_step,
-                 *self._ephemeral)
+                 *self._ephemeral, *((self.ema, self.ema_count) if self.ema is not None else ()))
         state = [t.clone() for t in saved]
         try:
             self._capture_graphs(exchange_in_graph)
@@ -663,6 +738,7 @@ class TrainStepEngine:
         """one micro-step (graph replay when captured); returns True when the optimizer stepped."""
         if self.graph_a is None:
             return self.step_eager()
+        self._refuse_ema_weights("step()")
         self._refuse_eval_batch()
         if self.exchange_in_graph and getattr(self.exchange, "closed", False):
             raise RuntimeError("the step's graph holds a collective on an RCCL communicator that has been closed (process "

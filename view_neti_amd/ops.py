@@ -425,6 +425,26 @@ def train_record(ring, count, rows, first_micro, timesteps, losses, Bn):
     _l.call("train_record", _p(ring), _p(count), rows, W, 1 if first_micro else 0, _p(timesteps), _p(losses), Bn, stream())
 
 
+EMA_HYPER_FLOATS, EMA_COEF_FLOATS = 4, 2  # {max_decay, update_after_step, power, 0}; {one_minus_decay, apply}
+
+
+def ema_update(ema, p, opt_step, ema_count, ema_hyper, ema_coef):
+    """one EMA update of the flat f32 range `ema` towards `p` (two launches: decay from the device counters, then the
+    update; nothing moves when the optimizer step before it was skipped).  Any 4-byte alignment of ema / p."""
+    assert ema.dtype == torch.float32 and p.dtype == torch.float32 and ema.is_contiguous() and p.is_contiguous()
+    assert ema.numel() == p.numel() and opt_step.dtype == torch.int32 and ema_count.dtype == torch.int32
+    assert ema_count.numel() >= 2 and ema_hyper.dtype == torch.float32 and ema_hyper.numel() >= EMA_HYPER_FLOATS
+    assert ema_coef.dtype == torch.float32 and ema_coef.numel() >= EMA_COEF_FLOATS
+    _l.call("ema_update", _p(ema), _p(p), ema.numel(), _p(opt_step), _p(ema_count), _p(ema_hyper), _p(ema_coef), stream())
+
+
+def swap_f32(a, b):
+    """exchange two flat f32 ranges element for element, bit for bit"""
+    assert a.dtype == torch.float32 and b.dtype == torch.float32 and a.is_contiguous() and b.is_contiguous()
+    assert a.numel() == b.numel()
+    _l.call("swap_f32", _p(a), _p(b), a.numel(), stream())
+
+
 def nested_dropout_mask(mask, nl, Bn, hidden, prob, state, stream_id):
     _l.call("nested_dropout_mask", _p(mask), nl, Bn, hidden, prob, _p(state), stream_id, stream())
 
