@@ -170,6 +170,12 @@ int vneti_transpose_f16_multi(const vneti_transpose_desc* descs, int n, void* st
  * Replaces: diffusers ResnetBlock2D.norm1/norm2 + nonlinearity, Transformer2DModel.norm,
  * conv_norm_out (driven from training/coach.py:197), forward and input-gradient.
  * ws: f32 workspace of vneti_groupnorm_ws_floats(...) floats.
+ * Accepted geometry, the same for every entry below (anything else: a negative status, or a negative size from
+ * vneti_groupnorm_ws_floats, and nothing written): C % 8 == 0, G <= 64, C % G == 0, C / G >= 4 and != 5 (with five
+ * channels per group an 8-channel chunk meets three groups; the kernels carry two), every ld % 8 == 0.
+ * Accuracy: mean and rstd are formed from f32 partial sums of x and x^2 (totals and E[x^2] - E[x]^2 in f64), so the 16-bit
+ * bars of the test-suite (y 2e-3, dx 4e-3 relative, rstd 1e-3) hold for |group mean| <= 64 group std; beyond that rstd
+ * loses digits as (mean / std)^2 — DESIGN.md section 6, "Norm kernels at their edges", has the measured table per path.
  * ------------------------------------------------------------------------------------------ */
 long long vneti_groupnorm_ws_floats(int Bn, int HW, int C, int G);
 int vneti_groupnorm_fwd(const void* x, long long ldx, void* y, long long ldy, const float* gamma,
@@ -202,6 +208,7 @@ int vneti_groupnorm_bwd(const void* dy, long long lddy, const void* x, long long
 
 /* ------------------------------------------------------------------------------------------
  * LayerNorm over the last dim of [rows][C]; x is f16 or f32, y is f16.
+ * Accepted: rows > 0, C % 8 == 0, C <= 2048, every ld % 8 == 0 (two-pass statistics: no bound on mean / std).
  * Replaces: BasicTransformerBlock.norm1/2/3 and CLIPEncoderLayer.layer_norm1/2,
  * final_layer_norm (models/neti_clip_text_encoder.py:183-185).
  * ------------------------------------------------------------------------------------------ */
@@ -257,7 +264,8 @@ int vneti_attn_bwd_small(const void* Q, long long ldq, const void* K, long long 
                          const void* dO, long long lddo, const void* O, long long ldo, const float* lse, void* dQ,
                          long long lddq, void* dK, long long lddk, void* dV, long long lddv, int Bn, int H, int N, int D,
                          float scale, int causal, void* stream);
-/* row softmax in place on f16 [rows][ld] (unfused attention of the VAE mid-block, d=512) */
+/* row softmax in place on f16 [rows][ld] (unfused attention of the VAE mid-block, d=512).
+ * Accepted: rows > 0, cols % 8 == 0, cols <= 16384, ld % 8 == 0. */
 int vneti_softmax_rows_f16(void* x, long long ld, int rows, int cols, void* stream);
 
 /* ------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """Per-kernel parity of the bf16 build: every case of the kernel files (tests/test_kernels_gpu.py, tests/test_text_kernels_gpu.py,
-tests/test_optim_rng_gpu.py, tests/test_kernel_contracts_gpu.py, tests/test_autotune_variants_gpu.py) against
+tests/test_optim_rng_gpu.py, tests/test_kernel_contracts_gpu.py, tests/test_autotune_variants_gpu.py,
+tests/test_norm_edges_gpu.py) against
 libvneti_hip_bf16.so.
 
 A process computes in ONE 16-bit format (view_neti_amd/lib.py), so the bf16 run of the kernel file is a child pytest
@@ -29,6 +30,7 @@ TEXT_FILE = os.path.join("tests", "test_text_kernels_gpu.py")
 OPTIM_RNG_FILE = os.path.join("tests", "test_optim_rng_gpu.py")
 CONTRACTS_FILE = os.path.join("tests", "test_kernel_contracts_gpu.py")
 VARIANTS_FILE = os.path.join("tests", "test_autotune_variants_gpu.py")
+NORM_EDGES_FILE = os.path.join("tests", "test_norm_edges_gpu.py")
 
 # group -> (kernel file, `-k` expression, time limit of the child in seconds).  The limits are several times the wall times
 # measured on an MI355X (the tables of the per-kernel parity runs), and never above 300 s.
@@ -51,9 +53,14 @@ GROUPS = {
     "variants_unet": (VARIANTS_FILE, "unet", 120),
     "variants_vae": (VARIANTS_FILE, "vae", 60),
     "variants_text": (VARIANTS_FILE, "text", 60),
+    # the norm kernels at their edges against float64 (group geometry, capacities, dtype paths, offset-dominated groups)
+    "edges_groupnorm": (NORM_EDGES_FILE, "edges_groupnorm", 60),
+    "edges_layernorm": (NORM_EDGES_FILE, "edges_layernorm", 60),
+    "edges_softmax": (NORM_EDGES_FILE, "edges_softmax", 60),
 }
 # kernel file -> the least number of cases its collection must hold (a file that lost its tests cannot pass as "covered")
-KERNEL_FILES = {KERNEL_FILE: 500, TEXT_FILE: 120, OPTIM_RNG_FILE: 30, CONTRACTS_FILE: 100, VARIANTS_FILE: 11}
+KERNEL_FILES = {KERNEL_FILE: 500, TEXT_FILE: 120, OPTIM_RNG_FILE: 30, CONTRACTS_FILE: 100, VARIANTS_FILE: 11,
+                NORM_EDGES_FILE: 140}
 
 
 def test_groups_cover_the_kernel_file():

@@ -11,7 +11,7 @@
 namespace {
 
 // ------------------------------------------------------------------------------------------
-// GroupNorm.  x: [B][HW][ldx] with C channels, G groups, cpg = C/G >= 4.
+// GroupNorm.  x: [B][HW][ldx] with C channels, G groups, cpg = C/G >= 4 and != 5 (gn_geom).
 // Work decomposition: block (slab, b) owns `rps` consecutive pixels of sample b.  Thread
 // (tx, ty) owns 8-channel chunk `tx` (looping in steps of TX when C/8 > 256) and walks rows
 // ty, ty+TY, ...  A chunk touches at most two groups ("lo"/"hi").
@@ -563,6 +563,10 @@ inline bool gn_use_small(int Bn, int HW, int C, int G, bool bwd) {
   return (long long)HW * cpg * 2 <= (bwd ? 32 : 40) * 1024 && Bn * G >= 64;
 }
 
+// 0, or why not: -1 the shape is outside the kernels' geometry; -2 cpg == 5.  Every kernel above gives an 8-channel chunk
+// two groups, lo and hi.  That holds for cpg = 4 (aligned), 6 and 7 (no reachable chunk offset meets three groups) and every
+// cpg >= 8, but not for cpg = 5: with C = 40, G = 8 the chunk of channels 8..15 holds the groups 1, 2 AND 3, and channel 15
+// would be counted and normalised with group 2.  (The GEMM epilogue sums refuse the same case, gemm_conv.hip.)
 int gn_geom(GNGeom& g, int Bn, int HW, int C, int G) {
   if (Bn <= 0 || HW <= 0 || C <= 0 || G <= 0 || G > 64 || C % G != 0 || C % 8 != 0) return -1;
   g.Bn = Bn;
@@ -571,6 +575,7 @@ int gn_geom(GNGeom& g, int Bn, int HW, int C, int G) {
   g.G = G;
   g.cpg = C / G;
   if (g.cpg < 4) return -1;
+  if (g.cpg == 5) return -2;
   g.CC = C / 8;
   g.TX = g.CC < 256 ? g.CC : 256;
   g.TY = 256 / g.TX;
@@ -587,6 +592,16 @@ int gn_geom(GNGeom& g, int Bn, int HW, int C, int G) {
   g.inv_n = 1.0 / ((double)HW * g.cpg);
   return 0;
 }
+
+#define GN_REQUIRE_GEOM(g, Bn, HW, C, G)                                                                                 \
+  do {                                                                                                                   \
+    const int geom_rc = gn_geom(g, Bn, HW, C, G);                                                                        \
+    VN_REQUIRE(geom_rc != -2,                                                                                            \
+               "groupnorm: C / G = 5 is not supported (B=%d HW=%d C=%d G=%d): an 8-channel chunk would meet three groups, " \
+               "the kernels carry two",                                                                                  \
+               Bn, HW, C, G);                                                                                            \
+    VN_REQUIRE(geom_rc == 0, "groupnorm: unsupported shape B=%d HW=%d C=%d G=%d", Bn, HW, C, G);                         \
+  } while (0)
 
 // ------------------------------------------------------------------------------------------
 // LayerNorm: one wave per row, up to 4 chunks of 8 elements per lane (C <= 2048).
@@ -837,7 +852,7 @@ extern "C" int vneti_groupnorm_fwd(const void* x, long long ldx, void* y, long l
                                    const float* beta, float* mean, float* rstd, float* ws, int Bn, int HW,
                                    int C, int G, float eps, int silu, void* stream) {
   GNGeom g;
-  VN_REQUIRE(gn_geom(g, Bn, HW, C, G) == 0, "groupnorm: unsupported shape B=%d HW=%d C=%d G=%d", Bn, HW, C, G);
+  GN_REQUIRE_GEOM(g, Bn, HW, C, G);
   VN_REQUIRE(x && y && gamma && beta && mean && rstd && ws, "groupnorm_fwd: null pointer");
   VN_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0, "groupnorm_fwd: ld must be a multiple of 8");
   VN_REQUIRE_OUT("groupnorm_fwd", vn_out_bytes((long long)Bn * HW, ldy, C, 2));
@@ -873,7 +888,7 @@ extern "C" int vneti_groupnorm_fwd_sums(const void* x, long long ldx, void* y, l
                                         int Bn, int HW, int C, int G, float eps, int silu, void* stream) {
   const float* sums = reinterpret_cast<const float*>(sums_v);  // 64-bit fixed-point words, see common.h (typed float* internally)
   GNGeom g;
-  VN_REQUIRE(gn_geom(g, Bn, HW, C, G) == 0, "groupnorm: unsupported shape B=%d HW=%d C=%d G=%d", Bn, HW, C, G);
+  GN_REQUIRE_GEOM(g, Bn, HW, C, G);
   VN_REQUIRE(x && y && gamma && beta && sums && mean && rstd && slots > 0, "groupnorm_fwd_sums: null pointer");
   VN_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0, "groupnorm_fwd_sums: ld % 8 != 0");
   VN_REQUIRE_OUT("groupnorm_fwd_sums", vn_out_bytes((long long)Bn * HW, ldy, C, 2));
@@ -900,7 +915,7 @@ extern "C" int vneti_groupnorm_fwd_2l(const void* x, long long ldx, void* y, lon
                                       int C, int G, float eps, int silu, void* stream) {
   float* sums = reinterpret_cast<float*>(sums_v);  // 64-bit fixed-point words, see common.h (typed float* internally)
   GNGeom g;
-  VN_REQUIRE(gn_geom(g, Bn, HW, C, G) == 0, "groupnorm: unsupported shape B=%d HW=%d C=%d G=%d", Bn, HW, C, G);
+  GN_REQUIRE_GEOM(g, Bn, HW, C, G);
   VN_REQUIRE(x && y && gamma && beta && mean && rstd && sums && slots > 0, "groupnorm_fwd_2l: null pointer");
   VN_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0, "groupnorm_fwd_2l: ld must be a multiple of 8");
   VN_REQUIRE_OUT("groupnorm_fwd_2l", vn_out_bytes((long long)Bn * HW, ldy, C, 2));
@@ -923,7 +938,7 @@ extern "C" int vneti_groupnorm_bwd(const void* dy, long long lddy, const void* x
                                    void* dx, long long lddx, const void* dx_accum, long long ldacc, float* ws,
                                    int Bn, int HW, int C, int G, int silu, void* stream) {
   GNGeom g;
-  VN_REQUIRE(gn_geom(g, Bn, HW, C, G) == 0, "groupnorm: unsupported shape B=%d HW=%d C=%d G=%d", Bn, HW, C, G);
+  GN_REQUIRE_GEOM(g, Bn, HW, C, G);
   VN_REQUIRE(dy && x && gamma && beta && mean && rstd && dx && ws, "groupnorm_bwd: null pointer");
   VN_REQUIRE(ldx % 8 == 0 && lddy % 8 == 0 && lddx % 8 == 0 && ldacc % 8 == 0, "groupnorm_bwd: ld % 8 != 0");
   VN_REQUIRE_OUT("groupnorm_bwd", vn_out_bytes((long long)Bn * HW, lddx, C, 2));
@@ -966,7 +981,7 @@ extern "C" int vneti_groupnorm_bwd_2l(const void* dy, long long lddy, const void
                                       int HW, int C, int G, int silu, void* stream) {
   float* sums = reinterpret_cast<float*>(sums_v);  // 64-bit fixed-point words, see common.h (typed float* internally)
   GNGeom g;
-  VN_REQUIRE(gn_geom(g, Bn, HW, C, G) == 0, "groupnorm: unsupported shape B=%d HW=%d C=%d G=%d", Bn, HW, C, G);
+  GN_REQUIRE_GEOM(g, Bn, HW, C, G);
   VN_REQUIRE(dy && x && gamma && beta && mean && rstd && dx && sums && slots > 0, "groupnorm_bwd_2l: null pointer");
   VN_REQUIRE(ldx % 8 == 0 && lddy % 8 == 0 && lddx % 8 == 0 && ldacc % 8 == 0, "groupnorm_bwd_2l: ld % 8 != 0");
   VN_REQUIRE_OUT("groupnorm_bwd_2l", vn_out_bytes((long long)Bn * HW, lddx, C, 2));
