@@ -233,6 +233,10 @@ int vneti_layernorm_bwd(const void* dy, int dy_is_f32, long long lddy, const voi
  * (models/xti_attention_processor.py:38-42: key from CONTEXT_TENSOR_l, value from
  * CONTEXT_TENSOR_BYPASS_l).  Replaces attn.get_attention_scores + torch.bmm (:48-49)
  * without materialising the score matrix.  lse: f32 [B][H][Nq] (natural log).
+ * Accepted, the same for every entry below (anything else: a negative status and nothing written): Bn, H, Nq, Nk > 0,
+ * D in {40, 64, 80, 160}, every input ld % 8 == 0 (output ld % 4 == 0), and every operand that is READ (Q, K, V, dO, O)
+ * under 2 GiB: Bn * N * ld * 2 < 0x7fffffff bytes.  The kernels read them through 32-bit buffer descriptors; from 2 GiB
+ * on a masked lane would read real memory and from 4 GiB on valid rows would read zeros, so the entries refuse.
  * ------------------------------------------------------------------------------------------ */
 int vneti_attn_fwd(const void* Q, long long ldq, const void* K, long long ldk, const void* V,
                    long long ldv, void* O, long long ldo, float* lse, int Bn, int H, int Nq,
@@ -256,6 +260,9 @@ int vneti_attn_bwd_dkv(const void* Q, long long ldq, const void* K, long long ld
 /* ws (optional f32 scratch): when the key side is short (cross-attention, Nk = 77) the query
  * range is split across workgroups and the f32 partials are reduced by a second kernel;
  * needs 2*qsplit*Bn*Nk*H*D floats (qsplit <= 32), NULL disables the split. */
+/* The number of query ranges vneti_attn_bwd_dkv takes for this shape with a workspace of ws_floats floats (1: no split,
+ * no reduce launch; the launcher calls the same function).  Negative: a shape the attention entries refuse. */
+int vneti_attn_dkv_qsplit(int Bn, int H, int Nq, int Nk, int D, int causal, long long ws_floats);
 /* dQ, dK and dV of a short self-attention in ONE launch: N <= 96 and D = 64 (the 77-token CLIP text encoder that
  * training/coach.py:289-305 runs once per UNet cross-attention layer, models/neti_clip_text_encoder.py:90-118), one
  * workgroup per (sequence, head) with Q, K, V, dO in LDS; bit-identical to vneti_attn_bwd_dq (O given) followed by

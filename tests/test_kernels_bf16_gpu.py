@@ -1,6 +1,6 @@
 """Per-kernel parity of the bf16 build: every case of the kernel files (tests/test_kernels_gpu.py, tests/test_text_kernels_gpu.py,
 tests/test_optim_rng_gpu.py, tests/test_kernel_contracts_gpu.py, tests/test_autotune_variants_gpu.py,
-tests/test_norm_edges_gpu.py, tests/test_conv_edges_gpu.py) against
+tests/test_norm_edges_gpu.py, tests/test_conv_edges_gpu.py, tests/test_attn_edges_gpu.py) against
 libvneti_hip_bf16.so.
 
 A process computes in ONE 16-bit format (view_neti_amd/lib.py), so the bf16 run of the kernel file is a child pytest
@@ -32,6 +32,7 @@ CONTRACTS_FILE = os.path.join("tests", "test_kernel_contracts_gpu.py")
 VARIANTS_FILE = os.path.join("tests", "test_autotune_variants_gpu.py")
 NORM_EDGES_FILE = os.path.join("tests", "test_norm_edges_gpu.py")
 CONV_EDGES_FILE = os.path.join("tests", "test_conv_edges_gpu.py")
+ATTN_EDGES_FILE = os.path.join("tests", "test_attn_edges_gpu.py")
 
 # group -> (kernel file, `-k` expression, time limit of the child in seconds).  The limits are several times the wall times
 # measured on an MI355X (the tables of the per-kernel parity runs), and never above 300 s.
@@ -62,10 +63,17 @@ GROUPS = {
     "edges_conv_select": (CONV_EDGES_FILE, "edges_conv_select", 60),
     "edges_conv_parity": (CONV_EDGES_FILE, "edges_conv_parity", 60),
     "edges_conv_small": (CONV_EDGES_FILE, "edges_conv_small", 60),
+    # the attention kernels at their tile edges against float64: ragged shapes, the online softmax on staircase data, the
+    # query split of dK/dV, the one-launch short backward, refusals
+    "edges_attn_ragged": (ATTN_EDGES_FILE, "edges_attn_ragged", 60),
+    "edges_attn_softmax": (ATTN_EDGES_FILE, "edges_attn_softmax", 60),
+    "edges_attn_qsplit": (ATTN_EDGES_FILE, "edges_attn_qsplit", 60),
+    "edges_attn_small": (ATTN_EDGES_FILE, "edges_attn_small", 60),
+    "edges_attn_refuse": (ATTN_EDGES_FILE, "edges_attn_refuse", 60),
 }
 # kernel file -> the least number of cases its collection must hold (a file that lost its tests cannot pass as "covered")
 KERNEL_FILES = {KERNEL_FILE: 500, TEXT_FILE: 120, OPTIM_RNG_FILE: 30, CONTRACTS_FILE: 100, VARIANTS_FILE: 11,
-                NORM_EDGES_FILE: 140, CONV_EDGES_FILE: 340}
+                NORM_EDGES_FILE: 140, CONV_EDGES_FILE: 340, ATTN_EDGES_FILE: 250}
 
 
 def test_groups_cover_the_kernel_file():

@@ -1004,6 +1004,36 @@ int check_common(int Bn, int H, int Nq, int Nk, int D) {
   return 0;
 }
 
+// Q, K, V, dO and O are read through 32-bit buffer descriptors (byte count cast to uint32_t, masked lanes at VN_OOB =
+// 2^31): from 2 GiB on a masked lane would read real memory, from 4 GiB on the count wraps and valid rows read zeros.
+// Bn * N * ld * 2 bytes < 0x7fffffff, evaluated without overflow (Bn, N > 0 checked by the caller)
+bool fits_descriptor(int Bn, int N, long long ld) {
+  return ld < (1LL << 40) && 2 * ld <= 0x7ffffffeLL / ((long long)Bn * N);
+}
+#define VN_REQUIRE_DESC(what, name, N, ld)                                                                        \
+  VN_REQUIRE(fits_descriptor(Bn, N, ld), "%s: %s spans %d x %d rows of ld %lld, over the 2 GiB range of the buffer loads", \
+             what, name, Bn, N, (long long)(ld))
+
+// dK/dV kernel: the number of query ranges per key block.  Few key blocks (cross-attention: Nk = 77) => split the query
+// range so the chip is filled; ws_floats bounds the f32 partials (2 * qsplit * Bn * Nk * H * D floats).
+int dkv_qsplit(int Bn, int H, int Nq, int Nk, int D, int causal, long long ws_floats) {
+  const int nkb = cdiv(Nk, 128), nqt = cdiv(Nq, 32 * DKV_QH(D));
+  const long long blocks = (long long)nkb * H * Bn;
+  int qsplit = 1;
+  // (also at exactly one 4-wave block per CU, the 32x32-latent self-attention: one wave per SIMD is latency-bound,
+  //  64 -> 57 us with the query range split in two, reduce launch included)
+  if (!causal && blocks <= 256 && nqt >= 8) {
+    qsplit = (int)(512 / blocks);
+    if (qsplit > nqt / 4) qsplit = nqt / 4;
+    if (qsplit > 32) qsplit = 32;
+    const long long plane = (long long)Bn * Nk * H * D;
+    // (the partials are stored through 32-bit buffer offsets: keep the slab under 4 GiB as well)
+    while (qsplit > 1 && (2LL * qsplit * plane > ws_floats || 8LL * qsplit * plane >= (1LL << 32) - 64)) --qsplit;
+    if (qsplit < 2) qsplit = 1;
+  }
+  return qsplit;
+}
+
 #define DISPATCH_D(KERNEL, grid, st, args)                                                   \
   switch (args.D) {                                                                          \
     case 40: hipLaunchKernelGGL((KERNEL<40>), grid, dim3(256), 0, st, args); break;          \
@@ -1029,6 +1059,9 @@ extern "C" int vneti_attn_fwd(const void* Q, long long ldq, const void* K, long 
   VN_REQUIRE(rc == 0, "attn_fwd: unsupported shape B=%d H=%d Nq=%d Nk=%d D=%d", Bn, H, Nq, Nk, D);
   VN_REQUIRE(Q && K && V && O, "attn_fwd: null pointer");
   VN_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0, "attn_fwd: bad strides");
+  VN_REQUIRE_DESC("attn_fwd", "Q", Nq, ldq);
+  VN_REQUIRE_DESC("attn_fwd", "K", Nk, ldk);
+  VN_REQUIRE_DESC("attn_fwd", "V", Nk, ldv);
   AttnArgs a;
   memset(&a, 0, sizeof(a));
   a.Q = (const half_t*)Q;
@@ -1057,7 +1090,12 @@ extern "C" int vneti_attn_fwd(const void* Q, long long ldq, const void* K, long 
 
 extern "C" int vneti_attn_bwd_delta(const void* dO, long long lddo, const void* O, long long ldo, float* delta,
                                     int Bn, int H, int Nq, int D, void* stream) {
-  VN_REQUIRE(dO && O && delta && Bn > 0 && H > 0 && Nq > 0 && D % 8 == 0, "attn_bwd_delta: bad arguments");
+  VN_REQUIRE(dO && O && delta, "attn_bwd_delta: null pointer");
+  VN_REQUIRE(check_common(Bn, H, Nq, 1, D) == 0, "attn_bwd_delta: unsupported shape B=%d H=%d Nq=%d D=%d", Bn, H, Nq, D);
+  VN_REQUIRE(lddo % 8 == 0 && ldo % 8 == 0, "attn_bwd_delta: bad strides");  // (16-byte row loads)
+  // (plain 64-bit loads here; the bound is the family's, so that what this entry accepts the dQ / dK/dV entries accept)
+  VN_REQUIRE_DESC("attn_bwd_delta", "dO", Nq, lddo);
+  VN_REQUIRE_DESC("attn_bwd_delta", "O", Nq, ldo);
   long long total = (long long)Bn * Nq * H;
   hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)cdivl(total, 256)), dim3(256), 0, (hipStream_t)stream,
                      (const half_t*)dO, lddo, (const half_t*)O, ldo, delta, Bn, H, Nq, D);
@@ -1075,6 +1113,11 @@ extern "C" int vneti_attn_bwd_dq(const void* Q, long long ldq, const void* K, lo
   VN_REQUIRE(!O || ldo % 8 == 0, "attn_bwd_dq: ldo must be a multiple of 8");
   VN_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && lddo % 8 == 0 && lddq % 4 == 0,
              "attn_bwd_dq: bad strides");
+  VN_REQUIRE_DESC("attn_bwd_dq", "Q", Nq, ldq);
+  VN_REQUIRE_DESC("attn_bwd_dq", "K", Nk, ldk);
+  VN_REQUIRE_DESC("attn_bwd_dq", "V", Nk, ldv);
+  VN_REQUIRE_DESC("attn_bwd_dq", "dO", Nq, lddo);
+  if (O) VN_REQUIRE_DESC("attn_bwd_dq", "O", Nq, ldo);
   AttnArgs a;
   memset(&a, 0, sizeof(a));
   a.Q = (const half_t*)Q;
@@ -1105,6 +1148,12 @@ extern "C" int vneti_attn_bwd_dq(const void* Q, long long ldq, const void* K, lo
   return vneti_check_launch("attn_bwd_dq");
 }
 
+extern "C" int vneti_attn_dkv_qsplit(int Bn, int H, int Nq, int Nk, int D, int causal, long long ws_floats) {
+  int rc = check_common(Bn, H, Nq, Nk, D);
+  VN_REQUIRE(rc == 0, "attn_dkv_qsplit: unsupported shape B=%d H=%d Nq=%d Nk=%d D=%d", Bn, H, Nq, Nk, D);
+  return dkv_qsplit(Bn, H, Nq, Nk, D, causal, ws_floats);
+}
+
 extern "C" int vneti_attn_bwd_dkv(const void* Q, long long ldq, const void* K, long long ldk, const void* V,
                                   long long ldv, const void* dO, long long lddo, const float* lse, const float* delta,
                                   void* dK, long long lddk, void* dV, long long lddv, int Bn, int H, int Nq,
@@ -1115,6 +1164,10 @@ extern "C" int vneti_attn_bwd_dkv(const void* Q, long long ldq, const void* K, l
   VN_REQUIRE(Q && K && V && dO && lse && delta && dK && dV, "attn_bwd_dkv: null pointer");
   VN_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && lddo % 8 == 0 && lddk % 4 == 0 && lddv % 4 == 0,
              "attn_bwd_dkv: bad strides");
+  VN_REQUIRE_DESC("attn_bwd_dkv", "Q", Nq, ldq);
+  VN_REQUIRE_DESC("attn_bwd_dkv", "K", Nk, ldk);
+  VN_REQUIRE_DESC("attn_bwd_dkv", "V", Nk, ldv);
+  VN_REQUIRE_DESC("attn_bwd_dkv", "dO", Nq, lddo);
   AttnArgs a;
   memset(&a, 0, sizeof(a));
   a.Q = (const half_t*)Q;
@@ -1138,21 +1191,8 @@ extern "C" int vneti_attn_bwd_dkv(const void* Q, long long ldq, const void* K, l
   a.D = D;
   a.scale = scale;
   a.causal = causal;
-  // few key blocks (cross-attention: Nk = 77) => split the query range so the chip is filled
-  const int nkb = cdiv(Nk, 128), nqt = cdiv(Nq, 32 * DKV_QH(D));
-  long long blocks = (long long)nkb * H * Bn;
-  int qsplit = 1;
-  // (also at exactly one 4-wave block per CU, the 32x32-latent self-attention: one wave per SIMD is latency-bound,
-  //  64 -> 57 us with the query range split in two, reduce launch included)
-  if (ws && !causal && blocks <= 256 && nqt >= 8) {
-    qsplit = (int)(512 / blocks);
-    if (qsplit > nqt / 4) qsplit = nqt / 4;
-    if (qsplit > 32) qsplit = 32;
-    const long long plane = (long long)Bn * Nk * H * D;
-    // (the partials are stored through 32-bit buffer offsets: keep the slab under 4 GiB as well)
-    while (qsplit > 1 && (2LL * qsplit * plane > ws_floats || 8LL * qsplit * plane >= (1LL << 32) - 64)) --qsplit;
-    if (qsplit < 2) qsplit = 1;
-  }
+  const int nkb = cdiv(Nk, 128);
+  const int qsplit = ws ? dkv_qsplit(Bn, H, Nq, Nk, D, causal, ws_floats) : 1;
   a.qsplit = qsplit;
   a.ws = ws;
   dim3 grid(nkb * qsplit, H, Bn);
@@ -1175,6 +1215,11 @@ extern "C" int vneti_attn_bwd_small(const void* Q, long long ldq, const void* K,
   if (N > 96 || D != 64) return VNETI_EUNSUP;  // longer sequences / other head sizes: vneti_attn_bwd_dq + vneti_attn_bwd_dkv
   VN_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && lddo % 8 == 0 && ldo % 8 == 0 && lddq % 4 == 0 && lddk % 4 == 0 &&
                  lddv % 4 == 0, "attn_bwd_small: bad strides");
+  VN_REQUIRE_DESC("attn_bwd_small", "Q", N, ldq);
+  VN_REQUIRE_DESC("attn_bwd_small", "K", N, ldk);
+  VN_REQUIRE_DESC("attn_bwd_small", "V", N, ldv);
+  VN_REQUIRE_DESC("attn_bwd_small", "dO", N, lddo);
+  VN_REQUIRE_DESC("attn_bwd_small", "O", N, ldo);
   AttnArgs a;
   memset(&a, 0, sizeof(a));
   a.Q = (const half_t*)Q;

@@ -125,7 +125,7 @@ GemmDesc, TransposeDesc = _STRUCTS["vneti_gemm_desc"], _STRUCTS["vneti_transpose
 SIGNATURES = {n[len("vneti_"):]: argtypes for n, (_, argtypes) in _PROTOS.items()}
 # the functions whose return value is a number to use (`query`); every other one returns a status (`call`)
 VALUE_FUNCS = frozenset({
-    "version", "precision", "last_error", "gemm_select_tile", "gemm_select_split", "img_resample_ksize",
+    "version", "precision", "last_error", "gemm_select_tile", "gemm_select_split", "attn_dkv_qsplit", "img_resample_ksize",
     "groupnorm_ws_floats", "lpips_ws_floats", "mse_loss_per_sample_ws_floats", "mapper_num_params", "mapper_save_floats",
     "mapper_rowgrad_floats", "mapper_legacy_input_params", "grad_sumsq_ws_doubles"})
 _stray = ({n[len("vneti_"):] for n, (res, _) in _PROTOS.items() if res is C.c_longlong} - VALUE_FUNCS) | (VALUE_FUNCS - set(SIGNATURES))

@@ -194,6 +194,11 @@ def attn_bwd_dkv(Q, K, V, dO, lse, delta, dK, dV, Bn, H, Nq, Nk, D, scale, causa
             ws.numel() if ws is not None else 0, stream())
 
 
+def attn_dkv_qsplit(Bn, H, Nq, Nk, D, causal, ws_floats):
+    """the number of query ranges attn_bwd_dkv takes with a workspace of `ws_floats` floats (1: no split)"""
+    return _l.query("attn_dkv_qsplit", Bn, H, Nq, Nk, D, 1 if causal else 0, ws_floats)
+
+
 def attn_bwd_small_ok(N, D):
     """sizes vneti_attn_bwd_small carries (the caller picks between it and attn_bwd_dq + attn_bwd_dkv)"""
     return N <= 96 and D == 64
