@@ -370,6 +370,39 @@ int vneti_cfg_sampler_step_noise(const void* pred, long long ldp, float* x, floa
 int vneti_cfg_sampler_step_noise_table(const void* pred, long long ldp, float* x, float* m_prev, float* x_in, int Bn,
                                        int Lc, int HW, float guidance, const float* coef_table,
                                        const float* noise_table, const int* step, int v_prediction, void* stream);
+/* Guidance rescale for the same loop (sd_pipeline_call.py:72-103: between the guidance combination, :96-98, and
+ * `scheduler.step`, :101).  Lin, Liu, Li & Yang 2023, "Common Diffusion Noise Schedules and Sample Steps are Flawed",
+ * section 3.4; diffusers' `guidance_rescale` argument, computed by `rescale_noise_cfg` (restated from the published code:
+ * parity against the package is unpinned).  Per sample b, over its Lc * HW elements, with the u, c and e = u + g (c - u)
+ * of vneti_cfg_sampler_step:
+ *   factor[b] = rescale * std(c[b]) / std(e[b]) + (1 - rescale)        rescale in [0, 1]
+ * (centred standard deviations; their N - 1 cancels).  The sums S(c), S(c^2), S(e), S(e^2) are accumulated in f64 (the
+ * square of an f32 is exact there), the centred sums, the ratio and the factor formed in f64 and rounded once to f32.
+ * Deterministic (two launches: per-chunk partials in a fixed order, then a finish; no float atomics), and factor[b] depends
+ * on sample b's data and (Lc, HW, guidance, rescale) only: not on Bn, not on b.  Deviation from diffusers: when the centred
+ * sum of squares of e[b] is not positive (a constant prediction) factor[b] = 1, where rescale_noise_cfg divides by zero.
+ * pred: 16-bit NHWC [2 Bn HW][ldp] (ldp >= Lc; Lc = 4 with ldp % 4 == 0 and an 8-byte aligned pred reads a pixel as one
+ * 8-byte load); factor: f32 [Bn]; ws: vneti_cfg_rescale_ws_doubles(Bn, HW) doubles, 8-byte aligned (negative: bad shape). */
+int vneti_cfg_rescale_factor(const void* pred, long long ldp, float* factor, void* ws, int Bn, int Lc, int HW,
+                             float guidance, float rescale, void* stream);
+long long vneti_cfg_rescale_ws_doubles(int Bn, int HW);
+/* The sampler step on the rescaled prediction (sd_pipeline_call.py:72-103, `scheduler.step` at :101 fed with
+ * rescale_noise_cfg's output): vneti_cfg_sampler_step_noise with one more operand,
+ *   e <- e * factor[b]      (one rounded f32 multiply between the guidance fma and x0; nothing else changes)
+ * factor: f32 [Bn], as vneti_cfg_rescale_factor writes it.  noise may be null: then there is no noise term and cn is
+ * ignored, so the entry serves eta = 0 and eta > 0.  factor[b] == 1 gives vneti_cfg_sampler_step_noise's x, m_prev and x_in
+ * bit for bit, and with cn = 0 or a null noise those of vneti_cfg_sampler_step.  The same 2 GiB bound on x_in. */
+int vneti_cfg_sampler_step_scaled(const void* pred, long long ldp, float* x, float* m_prev, float* x_in,
+                                  const float* noise, const float* factor, int Bn, int Lc, int HW, float guidance,
+                                  float alpha_t, float sigma_t, float cx, float c0, float c1, float cn, int v_prediction,
+                                  void* stream);
+/* hipGraph-replayable form of the scaled step (the captured sampler step of sd_pipeline_call.py:72-103): the scalars are row
+ * step[0] of the T x 6 table {alpha_t, sigma_t, cx, c0, c1, cn}; noise_table (f32 [T][B][Lc][HW], row step[0]) may be
+ * null: no noise term, the cn column is ignored. */
+int vneti_cfg_sampler_step_scaled_table(const void* pred, long long ldp, float* x, float* m_prev, float* x_in, int Bn,
+                                        int Lc, int HW, float guidance, const float* coef_table,
+                                        const float* noise_table, const float* factor, const int* step,
+                                        int v_prediction, void* stream);
 int vneti_table_fill_i64(void* dst_i64, int n, const void* table_i64, const int* step, void* stream);
 int vneti_counter_advance(int* counter, void* stream);
 /* AutoencoderKL.post_quant_conv on the latents scaled by 1/scaling_factor (pipeline.decode_latents):

@@ -22,6 +22,8 @@ ap.add_argument("--steps", type=int, default=30)
 ap.add_argument("--views", type=int, default=34)
 ap.add_argument("--seeds", type=int, default=2)
 ap.add_argument("--repeats", type=int, default=3)
+ap.add_argument("--guidance_rescale", type=float, default=0.0, help="diffusers' guidance_rescale (0: off)")
+ap.add_argument("--timestep_spacing", default=None, choices=["trailing"])
 a = ap.parse_args()
 cfg = sc.CONFIGS[a.model]()
 dev = "cuda"
@@ -57,7 +59,8 @@ def evaluation(eng, B):
                         torch.stack([vparams[c] for _, c, _ in entries]), slots=[o for o, _, _ in entries])
         lat = torch.cat([torch.randn((1, 4, eng.h, eng.w), generator=torch.Generator().manual_seed(s))
                          for _, _, s in entries])
-        img = eng.generate(lat, a.steps, 7.5, "dpm++2m")
+        img = eng.generate(lat, a.steps, 7.5, "dpm++2m", guidance_rescale=a.guidance_rescale,
+                           timestep_spacing=a.timestep_spacing)
         img[:n].cpu()  # what the driver does with each batch: the real entries go to the host
         n_img += n
     return n_img
@@ -86,7 +89,8 @@ for size in a.sizes.split(","):
             times[B].append(time.perf_counter() - t0)
     base = statistics.median(times[min(times)])
     out = {"metric": f"NVS evaluation images/s ({a.model} {W}x{H}, dpm++2m-{a.steps}, CFG, {a.views * a.seeds} "
-                     f"images = {a.views} views x {a.seeds} seeds)", "unit": "images/s", "arms": {}}
+                     f"images = {a.views} views x {a.seeds} seeds)", "unit": "images/s",
+           "guidance_rescale": a.guidance_rescale, "timestep_spacing": a.timestep_spacing, "arms": {}}
     for B, ts in times.items():
         med = statistics.median(ts)
         out["arms"][f"B{B}"] = {"images_per_s": n_img / med, "s_per_image": med / n_img, "speedup_vs_B1": base / med,

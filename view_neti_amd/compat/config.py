@@ -190,6 +190,10 @@ class EvalConfig:
     lpips_lin_weights: Optional[Path] = field(default=None, metadata={"ext": True, "run_control": True})
     # run the validation (images, and validation_nvs) on the EMA of the mappers (optim.ema_decay)
     validation_use_ema: bool = field(default=False, metadata={"ext": True, "run_control": True})
+    # the validation renders' sampler (Lin et al. 2023, for v-prediction models): diffusers' guidance_rescale in
+    # [0, 1] and the schedulers' timestep_spacing (None | "trailing").  They touch no training step.
+    guidance_rescale: float = field(default=0.0, metadata={"ext": True, "run_control": True})
+    timestep_spacing: Optional[str] = field(default=None, metadata={"ext": True, "run_control": True})
     # plain class attribute in the reference too (config.py:188)
     validation_view_tokens = None
 
@@ -200,6 +204,10 @@ class EvalConfig:
             "Length of validation_seeds should equal num_validation_images"
         if self.heldout_loss_steps < 0 or self.heldout_loss_timesteps < 1 or self.validation_nvs_batch < 1:
             raise ValueError("eval: heldout_loss_steps >= 0, heldout_loss_timesteps >= 1 and validation_nvs_batch >= 1")
+        if not 0.0 <= self.guidance_rescale <= 1.0:
+            raise ValueError(f"eval.guidance_rescale = {self.guidance_rescale}: it lies in [0, 1] (0: off)")
+        if self.timestep_spacing not in (None, "trailing"):
+            raise ValueError(f"eval.timestep_spacing {self.timestep_spacing!r}: None (the scheduler's default) or 'trailing'")
 
 
 @dataclass

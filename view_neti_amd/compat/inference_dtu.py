@@ -46,8 +46,15 @@ class InferenceConfig:
     lpips_lin_weights: Optional[Path] = None
     # evaluate the averaged mappers mapper-ema-steps-N_* of a run with optim.ema_decay instead of the raw ones
     use_ema: bool = False
+    # Lin et al. 2023 for v-prediction models sampled with guidance: diffusers' guidance_rescale in [0, 1]
+    # and the schedulers' timestep_spacing (None | "trailing"); both off by default
+    guidance_rescale: float = 0.0
+    timestep_spacing: Optional[str] = None
 
     def __post_init__(self):
+        from ..engine.infer import check_rescale, inference_timesteps
+        check_rescale(self.guidance_rescale)
+        inference_timesteps("ddim", 1, spacing=self.timestep_spacing)  # a bad string raises here, not after the load
         if self.do_lpips and (self.lpips_vgg_weights is None or self.lpips_lin_weights is None):
             raise ValueError("do_lpips needs --lpips_vgg_weights (torchvision vgg16-397923af.pth) and "
                              "--lpips_lin_weights (lpips weights/v0.1/vgg.pth)")
@@ -124,8 +131,10 @@ def prompt_for(view_token: str, object_token: str) -> str:
 
 
 def generate_views(pipe, pm, objects: Sequence[str], cam_idxs: Sequence[int], seeds: Sequence[int],
-                   num_denoising_steps: int, guidance_scale: float = 7.5) -> Dict[str, Dict[int, np.ndarray]]:
-    """object -> camidx -> uint8 (n_seeds, H, W, 3), all triples through batches of the engine's size"""
+                   num_denoising_steps: int, guidance_scale: float = 7.5,
+                   guidance_rescale: float = 0.0) -> Dict[str, Dict[int, np.ndarray]]:
+    """object -> camidx -> uint8 (n_seeds, H, W, 3), all triples through batches of the engine's size (the timestep
+    spacing is the pipeline's, `pipe.timestep_spacing`)"""
     from .sd_pipeline_call import sd_pipeline_call
     lut, _ = TextualInversionDataset.dtu_generate_dset_cam_tokens_params()
     B = pipe.engine.B
@@ -140,7 +149,8 @@ def generate_views(pipe, pm, objects: Sequence[str], cam_idxs: Sequence[int], se
         gens = [torch.Generator().manual_seed(s) for _, _, s in entries]
         # always the per-sample form (also at B = 1): it is what writes each sample's object slot
         out = sd_pipeline_call(pipe, prompts, num_inference_steps=num_denoising_steps, guidance_scale=guidance_scale,
-                               generator=gens, num_images_per_prompt=B, output_type="np", return_dict=False)[0]
+                               generator=gens, num_images_per_prompt=B, output_type="np", return_dict=False,
+                               guidance_rescale=guidance_rescale)[0]
         u8 = (out * 255).round().astype(np.uint8)
         for k in range(n):
             imgs[entries[k]] = u8[k]
@@ -253,7 +263,9 @@ def run(icfg: InferenceConfig) -> Dict[Optional[str], dict]:
     from .dtu_metrics import get_cam_idxs
     cam_idxs, _, _ = get_cam_idxs(train_cfg.data.dtu_subset)
     seeds = list(icfg.seeds)
-    preds = generate_views(pipe, pm, objects, cam_idxs, seeds, icfg.num_denoising_steps)
+    pipe.timestep_spacing = icfg.timestep_spacing
+    preds = generate_views(pipe, pm, objects, cam_idxs, seeds, icfg.num_denoising_steps,
+                           guidance_rescale=icfg.guidance_rescale)
     out_dir = Path(icfg.inference_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
     lpips_fn = None

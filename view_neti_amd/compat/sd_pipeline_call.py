@@ -17,6 +17,9 @@
                        randn((B, 4, h, w)) per sampler step from `generator`, after the initial latents and in step order
                        (a list of B generators: (1, 4, h, w) each from its own), as the scheduler's `variance_noise`;
                        with "dpm++2m" a non-zero eta raises (that scheduler has no eta; the reference drops it silently)
+    guidance_rescale -> not in the reference's signature: diffusers' StableDiffusionPipeline.__call__ argument of that name
+                       (Lin et al. 2023, `rescale_noise_cfg`), in [0, 1]; 0 (the default) is the reference's loop
+    timestep_spacing -> `pipeline.timestep_spacing`, a scheduler property like the sampler: None or "trailing"
 Returns an object with `.images` (list of PIL images, `output_type="pil"`) or the array, like the reference.
 """
 from __future__ import annotations
@@ -27,7 +30,7 @@ from typing import Any, Dict, List, Optional, Union
 import numpy as np
 import torch
 
-from ..engine.infer import InferenceEngine, check_eta
+from ..engine.infer import InferenceEngine, check_eta, check_rescale
 from .prompt_manager import PromptEmbeds
 
 
@@ -37,6 +40,7 @@ class InferencePipeline:
     tokenizer: Any
     sampler: str = "dpm++2m"
     object_slot: Optional[Dict[int, int]] = None  # object token id -> mapper slot of the engine's bucket (per-sample prompts)
+    timestep_spacing: Optional[str] = None  # the scheduler's timestep_spacing: None (its default list) or "trailing"
 
 
 @dataclass
@@ -90,7 +94,7 @@ def sd_pipeline_call(pipeline: InferencePipeline, prompt_embeds: Union[PromptEmb
                      negative_prompt: Optional[Union[str, List[str]]] = None, num_images_per_prompt: Optional[int] = 1,
                      eta: float = 0.0, generator: Optional[Union[torch.Generator, List[torch.Generator]]] = None,
                      latents: Optional[torch.Tensor] = None, output_type: Optional[str] = "pil",
-                     return_dict: bool = True):
+                     return_dict: bool = True, guidance_rescale: float = 0.0):
     eng = pipeline.engine
     B = eng.B
     H, W = eng.h * 8, eng.w * 8
@@ -99,6 +103,7 @@ def sd_pipeline_call(pipeline: InferencePipeline, prompt_embeds: Union[PromptEmb
     if num_images_per_prompt != B:
         raise ValueError(f"the engine was built for {B} images per call (num_images_per_prompt={num_images_per_prompt})")
     noisy = check_eta(pipeline.sampler, eta)  # eta != 0 on a sampler without one: ValueError, before any draw
+    check_rescale(guidance_rescale)  # outside [0, 1]: ValueError, before any draw
     neg = get_neg_prompt_input_ids(pipeline, negative_prompt)
     eng.set_negative_prompt(neg.input_ids)
     if latents is None:  # pipeline.prepare_latents: randn(shape, generator) * init_noise_sigma (= 1)
@@ -106,6 +111,10 @@ def sd_pipeline_call(pipeline: InferencePipeline, prompt_embeds: Union[PromptEmb
     # DDIMScheduler.step draws its variance noise inside the loop, after prepare_latents: one draw per step, in step order
     extra = dict(eta=eta, step_noise=torch.stack([_randn(eng, generator) for _ in range(num_inference_steps)])) \
         if noisy else {}
+    if guidance_rescale:
+        extra["guidance_rescale"] = guidance_rescale
+    if pipeline.timestep_spacing is not None:
+        extra["timestep_spacing"] = pipeline.timestep_spacing
     if isinstance(prompt_embeds, list) and prompt_embeds and all(isinstance(p, PromptEmbeds) for p in prompt_embeds):
         # one prompt per sample (distinct from the reference's list of per-step dicts: dispatch on the element type)
         set_prompt_list(pipeline, prompt_embeds)

@@ -68,7 +68,8 @@ class ValidationHandler:
             m.output_bypass_alpha_object, hidden_object=first.hidden, unconstrained_object=m.bypass_unconstrained_object,
             device=eng.dev, params_object=eng.params[: eng.n_all_obj], object_slot=self.slot,
             object_slot_stride=eng.n_obj, **first.engine_encoder_kwargs(), **kw)
-        self.pipeline = InferencePipeline(self.engine, coach.tokenizer, "dpm++2m")
+        self.pipeline = InferencePipeline(self.engine, coach.tokenizer, "dpm++2m",
+                                          timestep_spacing=self.cfg.eval.timestep_spacing)
         self.prompt_manager = PromptManager(
             coach.tokenizer, placeholder_view_token_ids=coach.placeholder_view_token_ids,
             placeholder_object_token_ids=coach.placeholder_object_token_ids,
@@ -117,7 +118,8 @@ class ValidationHandler:
             device=eng.dev, params_object=eng.params[: eng.n_all_obj], object_slot_stride=eng.n_obj, per_sample_slots=True,
             **first.engine_encoder_kwargs(), **self._view_kwargs())
         # this tokenizer's object ids -> the trainer's slots (slot k = k-th placeholder object token, as in the Coach)
-        self.pipeline = InferencePipeline(self.engine, tok, "dpm++2m", object_slot={tid: k for k, tid in enumerate(object_ids)})
+        self.pipeline = InferencePipeline(self.engine, tok, "dpm++2m", object_slot={tid: k for k, tid in enumerate(object_ids)},
+                                          timestep_spacing=ev.timestep_spacing)
         self.pipeline.object_tokens = object_tokens
         id2tok = dict(zip(view_ids, view_tokens))
         mv = coach.mapper_view
@@ -161,7 +163,7 @@ class ValidationHandler:
         stem = f"validation-iter_{step}-denoisesteps_{ev.num_denoising_steps}"
         base = f"{stem}_numseeds_{len(seeds)}_upsample_{ev.dtu_upsample_key}"
         preds = nvs.generate_views(self.pipeline, self.prompt_manager, self.nvs_objects, self.nvs_cams, seeds,
-                                   ev.num_denoising_steps)
+                                   ev.num_denoising_steps, guidance_rescale=ev.guidance_rescale)
         objs = self.nvs_objects
         torch.save(preds[objs[0]] if len(objs) == 1 else {o: preds[o] for o in objs}, exp / f"{base}.pt")
         figures = importlib.util.find_spec("matplotlib") is not None
@@ -191,7 +193,7 @@ class ValidationHandler:
         for seed in seeds:
             img = sd_pipeline_call(self.pipeline, emb, num_inference_steps=self.cfg.eval.num_denoising_steps,
                                    generator=torch.Generator().manual_seed(seed), output_type="np",
-                                   return_dict=False)[0]
+                                   return_dict=False, guidance_rescale=self.cfg.eval.guidance_rescale)[0]
             out.append((img[0] * 255).round().astype(np.uint8))
         return out
 

@@ -310,13 +310,18 @@ __global__ void cfg_sampler_step_table_kernel(const half_t* pred, long long ldp,
 // split c1 m_prev off into a rounded product and an add).  So contraction is off in this body and every fma of that
 // kernel's ISA is written out: e = fma(g, c-u, u); x0 = fma(-sigma_t, e, x) / alpha_t (IEEE division), or
 // alpha_t x - sigma_t e with both products rounded; r = fma(c1, m_prev, fma(cx, x, c0 x0)).
+//
+// SCALED (guidance rescale, the _scaled entries): e <- e * factor[b] as one rounded multiply of its own between the
+// guidance fma and x0, factor[b] written by cfg_rescale_finish_kernel; a factor of exactly 1 changes no bit.  There `noise`
+// may be null (eta = 0): nothing is loaded through it and cn is not looked at.  SCALED = false is the body as it was.
 struct StepCoef {
   float alpha_t, sigma_t, cx, c0, c1, cn;
 };
-template <int V>
+template <int V, bool SCALED = false>
 __device__ __forceinline__ void cfg_sampler_step_noise_body(const half_t* pred, long long ldp, float* x, float* m_prev,
                                                             float* x_in, const float* noise, int Bn, int Lc, int HW,
-                                                            float guidance, const StepCoef k, int vpred) {
+                                                            float guidance, const StepCoef k, int vpred,
+                                                            const float* factor = nullptr) {
 #pragma clang fp contract(off)
   const int total = Bn * Lc * HW;
   const int gid = (blockIdx.x * blockDim.x + threadIdx.x) * V;
@@ -328,12 +333,16 @@ __device__ __forceinline__ void cfg_sampler_step_noise_body(const half_t* pred, 
   if constexpr (V == 4) {
     const f32x4 a = *reinterpret_cast<const f32x4*>(x + gid);
     const f32x4 m = *reinterpret_cast<const f32x4*>(m_prev + gid);
-    const f32x4 n = *reinterpret_cast<const f32x4*>(noise + gid);
+    f32x4 n = {0.f, 0.f, 0.f, 0.f};
+    if (!SCALED || noise) n = *reinterpret_cast<const f32x4*>(noise + gid);
 #pragma unroll
     for (int j = 0; j < 4; ++j) xv[j] = a[j], mp[j] = m[j], nz[j] = n[j];
   } else {
-    xv[0] = x[gid], mp[0] = m_prev[gid], nz[0] = noise[gid];
+    xv[0] = x[gid], mp[0] = m_prev[gid], nz[0] = (!SCALED || noise) ? noise[gid] : 0.f;
   }
+  const bool with_noise = k.cn != 0.f && (!SCALED || noise);
+  float fb = 1.f;
+  if constexpr (SCALED) fb = factor[b];
   const half_t* pu = pred + ((long long)b * HW + p) * ldp + c;
   const half_t* pc = pred + ((long long)(Bn + b) * HW + p) * ldp + c;
 #pragma unroll
@@ -341,9 +350,10 @@ __device__ __forceinline__ void cfg_sampler_step_noise_body(const half_t* pred, 
     float u = (float)pu[j * ldp];
     float cnd = (float)pc[j * ldp];
     float e = fmaf(guidance, cnd - u, u);
+    if constexpr (SCALED) e = e * fb;
     x0[j] = vpred ? (k.alpha_t * xv[j] - k.sigma_t * e) : fmaf(-k.sigma_t, e, xv[j]) / k.alpha_t;
     float r = fmaf(k.c1, mp[j], fmaf(k.cx, xv[j], k.c0 * x0[j]));
-    xn[j] = k.cn != 0.f ? fmaf(k.cn, nz[j], r) : r;
+    xn[j] = with_noise ? fmaf(k.cn, nz[j], r) : r;
   }
   if constexpr (V == 4) {
     const f32x4 o = {xn[0], xn[1], xn[2], xn[3]}, d = {x0[0], x0[1], x0[2], x0[3]};
@@ -379,6 +389,104 @@ __global__ __launch_bounds__(256) void cfg_sampler_step_noise_table_kernel(const
   const StepCoef k = {cf[0], cf[1], cf[2], cf[3], cf[4], cf[5]};
   cfg_sampler_step_noise_body<V>(pred, ldp, x, m_prev, x_in, noise_table + (long long)s * Bn * Lc * HW, Bn, Lc, HW,
                                  guidance, k, vpred);
+}
+// guidance rescale: the same two forms with e * factor[b]; noise / noise_table may be null
+template <int V>
+__global__ __launch_bounds__(256) void cfg_sampler_step_scaled_kernel(const half_t* pred, long long ldp, float* x,
+                                                                      float* m_prev, float* x_in, const float* noise,
+                                                                      const float* factor, int Bn, int Lc, int HW,
+                                                                      float guidance, StepCoef k, int vpred) {
+  cfg_sampler_step_noise_body<V, true>(pred, ldp, x, m_prev, x_in, noise, Bn, Lc, HW, guidance, k, vpred, factor);
+}
+template <int V>
+__global__ __launch_bounds__(256) void cfg_sampler_step_scaled_table_kernel(const half_t* pred, long long ldp, float* x,
+                                                                            float* m_prev, float* x_in, int Bn, int Lc,
+                                                                            int HW, float guidance, const float* coef_table,
+                                                                            const float* noise_table, const float* factor,
+                                                                            const int* step, int vpred) {
+  const int s = step[0];
+  const float* cf = coef_table + 6 * s;
+  const StepCoef k = {cf[0], cf[1], cf[2], cf[3], cf[4], cf[5]};
+  cfg_sampler_step_noise_body<V, true>(pred, ldp, x, m_prev, x_in,
+                                       noise_table ? noise_table + (long long)s * Bn * Lc * HW : nullptr, Bn, Lc, HW,
+                                       guidance, k, vpred, factor);
+}
+
+// ---- guidance rescale factor (Lin et al. 2023, section 3.4; diffusers' rescale_noise_cfg) -------------------------------
+// f[b] = phi * std(c[b]) / std(e[b]) + (1 - phi) over the Lc * HW elements of sample b, with the very u, c and
+// e = fma(g, c - u, u) the step body above forms (contraction off here too).  Both standard deviations are centred and the
+// N - 1 of both cancels, so f needs the four sums S(c), S(c^2), S(e), S(e^2) only.  They are taken in f64: the square of
+// an f32 is exact in f64, so the only rounding is that of the f64 additions, and S(v^2) - S(v)^2 / N keeps ~16 digits minus
+// log10(1 + mean^2 / var) (a prediction of mean 3 and deviation 1 loses one).  Two stages in a FIXED order, no float atomics
+// and no "last block" counter (as mse_per_sample_kernel): block (chunk, b) owns the kRescaleChunk pixels
+// [chunk * kRescaleChunk, ...) of sample b; thread t takes pixels t, t + 256, ... of the chunk, channels in order; the four
+// sums go down the wave64 by shuffles (offsets 32, 16, .. 1), then lane 0 of each wave leaves them in LDS and thread 0 adds
+// the waves in wave order; ws[(b * nchunk + chunk) * 4 + {0..3}] is the partial.  The finish adds a sample's partials in
+// chunk order, forms the centred sums, the ratio and f in f64 and rounds ONCE to f32.  The partition depends on HW alone:
+// f[b] is a function of sample b's data and (Lc, HW, g, phi), whatever Bn and wherever b sits.  A prediction whose centred
+// sum of squares of e is not positive (a constant e[b]) gets f = 1, where diffusers divides by zero.
+// VEC: Lc == 4, ldp % 4 == 0 and an 8-byte aligned base: the four channels of a pixel are one 8-byte load per CFG half.
+constexpr int kRescaleChunk = 512;
+template <bool VEC>
+__global__ __launch_bounds__(256) void cfg_rescale_partial_kernel(const half_t* __restrict__ pred, long long ldp,
+                                                                  double* __restrict__ ws, int Bn, int Lc, int HW,
+                                                                  int nchunk, float guidance) {
+#pragma clang fp contract(off)
+  __shared__ double red[4][4];
+  const int chunk = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+  double s[4] = {0.0, 0.0, 0.0, 0.0};  // S(c), S(c^2), S(e), S(e^2)
+#pragma unroll
+  for (int j = 0; j < kRescaleChunk / 256; ++j) {
+    const int p = chunk * kRescaleChunk + j * 256 + t;
+    if (p < HW) {
+      const half_t* pu = pred + ((long long)b * HW + p) * ldp;
+      const half_t* pc = pred + ((long long)(Bn + b) * HW + p) * ldp;
+      if constexpr (VEC) {
+        const half4 u4 = *reinterpret_cast<const half4*>(pu);
+        const half4 c4 = *reinterpret_cast<const half4*>(pc);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const float u = (float)u4[c], cnd = (float)c4[c];
+          const double cd = (double)cnd, ed = (double)fmaf(guidance, cnd - u, u);
+          s[0] += cd, s[1] += cd * cd, s[2] += ed, s[3] += ed * ed;
+        }
+      } else {
+        for (int c = 0; c < Lc; ++c) {
+          const float u = (float)pu[c], cnd = (float)pc[c];
+          const double cd = (double)cnd, ed = (double)fmaf(guidance, cnd - u, u);
+          s[0] += cd, s[1] += cd * cd, s[2] += ed, s[3] += ed * ed;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s[k] += __shfl_down(s[k], off, 64);
+  }
+  if ((t & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) red[t >> 6][k] = s[k];
+  }
+  __syncthreads();
+  if (t < 4) ws[((long long)b * nchunk + chunk) * 4 + t] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+}
+__global__ __launch_bounds__(256) void cfg_rescale_finish_kernel(const double* __restrict__ ws, int Bn, int nchunk,
+                                                                 double n_elem, float rescale, float* __restrict__ factor) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= Bn) return;
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int k = 0; k < nchunk; ++k) {
+    const double* w = ws + ((long long)b * nchunk + k) * 4;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) s[q] += w[q];
+  }
+  const double ss_c = s[1] - s[0] * s[0] / n_elem, ss_e = s[3] - s[2] * s[2] / n_elem;
+  const double phi = (double)rescale;
+  double f = 1.0;
+  if (ss_e > 0.0) f = phi * sqrt(fmax(ss_c, 0.0) / ss_e) + (1.0 - phi);
+  factor[b] = (float)f;
 }
 __global__ void table_fill_i64_kernel(long long* dst, int n, const long long* table, const int* step) {
   int gid = blockIdx.x * blockDim.x + threadIdx.x;
@@ -913,6 +1021,71 @@ extern "C" int vneti_cfg_sampler_step_noise_table(const void* pred, long long ld
                        (const half_t*)pred, ldp, x, m_prev, x_in, Bn, Lc, HW, guidance, coef_table, noise_table, step,
                        v_prediction);
   return vneti_check_launch("cfg_sampler_step_noise_table");
+}
+
+extern "C" long long vneti_cfg_rescale_ws_doubles(int Bn, int HW) {
+  if (Bn <= 0 || HW <= 0) return -1;
+  return 4LL * Bn * cdiv(HW, kRescaleChunk);
+}
+
+extern "C" int vneti_cfg_rescale_factor(const void* pred, long long ldp, float* factor, void* ws, int Bn, int Lc, int HW,
+                                        float guidance, float rescale, void* stream) {
+  VN_REQUIRE(pred && factor && ws, "cfg_rescale_factor: null pointer");
+  VN_REQUIRE(Bn > 0 && Bn <= 65535 && Lc > 0 && HW > 0 && ldp >= Lc,
+             "cfg_rescale_factor: bad shape Bn=%d Lc=%d HW=%d ldp=%lld (0 < Bn <= 65535, ldp >= Lc)", Bn, Lc, HW, ldp);
+  VN_REQUIRE((long long)Bn * Lc * HW < 0x7fffffffLL, "cfg_rescale_factor: Bn * Lc * HW over 2^31");
+  VN_REQUIRE(((uintptr_t)ws & 7u) == 0, "cfg_rescale_factor: ws must be 8-byte aligned");
+  VN_REQUIRE(rescale >= 0.f && rescale <= 1.f, "cfg_rescale_factor: rescale = %g outside [0, 1]", (double)rescale);
+  const int nchunk = cdiv(HW, kRescaleChunk);
+  if (Lc == 4 && ldp % 4 == 0 && ((uintptr_t)pred & 7u) == 0)
+    hipLaunchKernelGGL(cfg_rescale_partial_kernel<true>, dim3(nchunk, Bn), dim3(256), 0, ST, (const half_t*)pred, ldp,
+                       (double*)ws, Bn, Lc, HW, nchunk, guidance);
+  else
+    hipLaunchKernelGGL(cfg_rescale_partial_kernel<false>, dim3(nchunk, Bn), dim3(256), 0, ST, (const half_t*)pred, ldp,
+                       (double*)ws, Bn, Lc, HW, nchunk, guidance);
+  const int rc = vneti_check_launch("cfg_rescale_factor");
+  if (rc != VNETI_OK) return rc;
+  hipLaunchKernelGGL(cfg_rescale_finish_kernel, dim3(cdiv(Bn, 256)), dim3(256), 0, ST, (const double*)ws, Bn, nchunk,
+                     (double)Lc * (double)HW, rescale, factor);
+  return vneti_check_launch("cfg_rescale_factor_finish");
+}
+
+extern "C" int vneti_cfg_sampler_step_scaled(const void* pred, long long ldp, float* x, float* m_prev, float* x_in,
+                                             const float* noise, const float* factor, int Bn, int Lc, int HW,
+                                             float guidance, float alpha_t, float sigma_t, float cx, float c0, float c1,
+                                             float cn, int v_prediction, void* stream) {
+  VN_REQUIRE(pred && x && m_prev && x_in && factor && Bn > 0 && Lc > 0 && HW > 0 && ldp >= Lc && alpha_t > 0.f,
+             "cfg_sampler_step_scaled: bad arguments");
+  const long long n = (long long)Bn * Lc * HW;
+  VN_REQUIRE_OUT("cfg_sampler_step_scaled (x_in)", 2 * n * 4);
+  const StepCoef k = {alpha_t, sigma_t, cx, c0, c1, cn};
+  if (step_noise_vec4(HW, x, m_prev, x_in, noise))
+    hipLaunchKernelGGL(cfg_sampler_step_scaled_kernel<4>, dim3(cdiv((int)(n / 4), 256)), dim3(256), 0, ST,
+                       (const half_t*)pred, ldp, x, m_prev, x_in, noise, factor, Bn, Lc, HW, guidance, k, v_prediction);
+  else
+    hipLaunchKernelGGL(cfg_sampler_step_scaled_kernel<1>, dim3(cdiv((int)n, 256)), dim3(256), 0, ST, (const half_t*)pred,
+                       ldp, x, m_prev, x_in, noise, factor, Bn, Lc, HW, guidance, k, v_prediction);
+  return vneti_check_launch("cfg_sampler_step_scaled");
+}
+
+extern "C" int vneti_cfg_sampler_step_scaled_table(const void* pred, long long ldp, float* x, float* m_prev, float* x_in,
+                                                   int Bn, int Lc, int HW, float guidance, const float* coef_table,
+                                                   const float* noise_table, const float* factor, const int* step,
+                                                   int v_prediction, void* stream) {
+  VN_REQUIRE(pred && x && m_prev && x_in && coef_table && factor && step && Bn > 0 && Lc > 0 && HW > 0 && ldp >= Lc,
+             "cfg_sampler_step_scaled_table: bad arguments");
+  const long long n = (long long)Bn * Lc * HW;
+  VN_REQUIRE_OUT("cfg_sampler_step_scaled_table (noise_table row)", n * 4);
+  VN_REQUIRE_OUT("cfg_sampler_step_scaled_table (x_in)", 2 * n * 4);
+  if (step_noise_vec4(HW, x, m_prev, x_in, noise_table))
+    hipLaunchKernelGGL(cfg_sampler_step_scaled_table_kernel<4>, dim3(cdiv((int)(n / 4), 256)), dim3(256), 0, ST,
+                       (const half_t*)pred, ldp, x, m_prev, x_in, Bn, Lc, HW, guidance, coef_table, noise_table, factor,
+                       step, v_prediction);
+  else
+    hipLaunchKernelGGL(cfg_sampler_step_scaled_table_kernel<1>, dim3(cdiv((int)n, 256)), dim3(256), 0, ST,
+                       (const half_t*)pred, ldp, x, m_prev, x_in, Bn, Lc, HW, guidance, coef_table, noise_table, factor,
+                       step, v_prediction);
+  return vneti_check_launch("cfg_sampler_step_scaled_table");
 }
 
 extern "C" int vneti_table_fill_i64(void* dst, int n, const void* table, const int* step, void* stream) {

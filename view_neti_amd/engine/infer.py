@@ -14,6 +14,9 @@ holds T dicts of 32 tensors) but produced per step, 16 layers at a time; the unc
 once.  Samplers: DPM-Solver++(2M) (the scheduler validate.py:568 / inference_dtu.py:304 install) and DDIM,
 both as x <- cx x + c0 x0 + c1 x0_prev on the data prediction; DDIM with eta > 0 adds cn * noise, the noise of each step
 read from a device table so that the step still replays as one graph (vneti_cfg_sampler_step_noise_table).
+Guidance rescale (Lin et al. 2023; diffusers' `guidance_rescale`) multiplies the guided prediction of sample b by
+f[b] = phi std(cond[b]) / std(guided[b]) + 1 - phi before the step: vneti_cfg_rescale_factor (two launches) and the
+scaled step entries replace the step launch, in the eager loop and inside the captured step alike.
 """
 from __future__ import annotations
 
@@ -31,16 +34,24 @@ from .unet import UNetEngine
 from .vae import VAEDecoderEngine
 
 
-def inference_timesteps(kind: str, num_steps: int, num_train: int = 1000) -> List[int]:
+def inference_timesteps(kind: str, num_steps: int, num_train: int = 1000, spacing: Optional[str] = None) -> List[int]:
     """DPMSolverMultistepScheduler.set_timesteps: linspace(0, T-1, N+1).round()[::-1][:-1];
-    DDIMScheduler.set_timesteps with steps_offset=1 (the SD scheduler configs): arange(N)*(T//N) reversed + 1."""
+    DDIMScheduler.set_timesteps with steps_offset=1 (the SD scheduler configs): arange(N)*(T//N) reversed + 1.
+    spacing="trailing" (both schedulers' timestep_spacing; Lin et al. 2023, "sample from the last timestep"):
+    round(arange(T, 0, -T/N)) - 1, which starts at T - 1; None keeps the lists above."""
+    import numpy as np
+    if kind not in ("dpm++2m", "ddim"):
+        raise ValueError(f"unknown sampler {kind!r} (dpm++2m | ddim)")
+    if spacing == "trailing":
+        if not 0 < num_steps <= num_train:
+            raise ValueError(f"{num_steps} trailing timesteps out of {num_train}")
+        return [int(t) for t in np.round(np.arange(num_train, 0, -num_train / num_steps)).astype(np.int64) - 1]
+    if spacing is not None:
+        raise ValueError(f"timestep_spacing {spacing!r}: None (the scheduler's default) or 'trailing'")
     if kind == "dpm++2m":
-        import numpy as np
         return [int(t) for t in np.linspace(0, num_train - 1, num_steps + 1).round()[::-1][:-1].astype(np.int64)]
-    if kind == "ddim":
-        ratio = num_train // num_steps
-        return [i * ratio + 1 for i in range(num_steps)][::-1]
-    raise ValueError(f"unknown sampler {kind!r} (dpm++2m | ddim)")
+    ratio = num_train // num_steps
+    return [i * ratio + 1 for i in range(num_steps)][::-1]
 
 
 def coefficient_row(kind: str, ac: torch.Tensor, timesteps: Sequence[int], i: int, eta: float = 0.0):
@@ -97,6 +108,15 @@ def check_eta(kind: str, eta: float) -> bool:
     if eta < 0:
         raise ValueError(f"eta = {eta}: DDIM's eta lies in [0, 1]")
     return True
+
+
+def check_rescale(guidance_rescale: float) -> bool:
+    """True when the step needs the rescale factor (phi > 0); phi outside [0, 1] raises (diffusers takes any float: phi
+    weighs the rescaled against the plain guided prediction, and nothing outside [0, 1] is a weight)"""
+    phi = float(guidance_rescale)
+    if not 0.0 <= phi <= 1.0:  # (NaN fails both comparisons)
+        raise ValueError(f"guidance_rescale = {guidance_rescale}: it lies in [0, 1] (0: off, 0.7: the paper's value)")
+    return phi > 0.0
 
 
 _BUFFER_RANGE = 0x7fffffff  # bytes a buffer-resource store can address (csrc/common.h VN_REQUIRE_OUT)
@@ -198,7 +218,12 @@ class InferenceEngine:
         # at the first such call
         self.coef_table6 = torch.zeros((cfg.ddpm.num_train_timesteps, 6), dtype=torch.float32, device=device)
         self.noise_table = None
-        # captured sampler steps by (guidance_scale, vpred, noisy): one with and one without the noise term at a time
+        # guidance rescale (phi > 0): f[b] f32 [B] and the f64 partials of its reduction, allocated at the first such call
+        # (their size is fixed by the engine's shape: once)
+        self.rescale_factor = None
+        self.rescale_ws = None
+        # captured sampler steps by (guidance_scale, vpred, noisy), plus (phi,) when phi > 0: one per (noisy, rescaled) at a
+        # time
         self._graphs = {}
 
     # ------------------------------------------------------------------ conditioning
@@ -256,18 +281,23 @@ class InferenceEngine:
     @torch.no_grad()
     def generate(self, latents: torch.Tensor, num_inference_steps: int = 50, guidance_scale: float = 7.5,
                  kind: str = "dpm++2m", decode: bool = True, use_graph: bool = True, eta: float = 0.0,
-                 step_noise: Optional[torch.Tensor] = None):
+                 step_noise: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0,
+                 timestep_spacing: Optional[str] = None):
         """latents: (B, 4, h, w) N(0,1) draw (`prepare_latents`, init_noise_sigma = 1 for both samplers).
         eta > 0 (DDIM only): DDIMScheduler.step's variance term, fed from step_noise, f32 [T][B][4][h][w] N(0,1) (one draw
         per sampler step; None: drawn here from torch's global generator, as the scheduler does without a generator).
+        guidance_rescale in [0, 1] (diffusers' argument): the guided prediction of each sample is scaled by
+        phi std(cond) / std(guided) + 1 - phi before the step; 0 is off and launches what it always did.
+        timestep_spacing: None (the schedulers' lists) or "trailing".
         Returns the images f32 [B, H, W, 3] in [0,1] (the array `numpy_to_pil` receives) or the final latents."""
-        ts = self._timesteps(kind, num_inference_steps, guidance_scale)
-        return self._sample(latents, ts, guidance_scale, kind, decode, eta, step_noise, self._own_conditioning, use_graph)
+        ts = self._timesteps(kind, num_inference_steps, guidance_scale, timestep_spacing)
+        return self._sample(latents, ts, guidance_scale, kind, decode, eta, step_noise, self._own_conditioning, use_graph,
+                            guidance_rescale)
 
-    def _timesteps(self, kind, num_inference_steps, guidance_scale):
+    def _timesteps(self, kind, num_inference_steps, guidance_scale, spacing=None):
         if guidance_scale <= 1.0:
             raise ValueError("sd_pipeline_call only defines the classifier-free-guidance branch (guidance_scale > 1)")
-        return inference_timesteps(kind, num_inference_steps, self.cfg.ddpm.num_train_timesteps)
+        return inference_timesteps(kind, num_inference_steps, self.cfg.ddpm.num_train_timesteps, spacing)
 
     def _own_conditioning(self, i, t):
         """eager step i at timestep t: the engine's text pass writes the conditional half of the UNet's contexts"""
@@ -278,26 +308,33 @@ class InferenceEngine:
         self.unet.ctx_k[:, B * L:].copy_(self.ctx_k)
         self.unet.ctx_v[:, B * L:].copy_(self.ctx_v)
 
-    def _sample(self, latents, ts, guidance_scale, kind, decode, eta, step_noise, conditioning, use_graph):
+    def _sample(self, latents, ts, guidance_scale, kind, decode, eta, step_noise, conditioning, use_graph,
+                guidance_rescale=0.0):
         """the sampler loop behind generate() and generate_from_contexts().  conditioning(i, t) sets the timestep and the
         conditional contexts of eager step i; use_graph replays one captured step instead (which runs the engine's own
         text pass: timesteps and step scalars come from device tables).  eta > 0 (`noisy`) swaps the sampler launch for
-        its noise-table sibling and nothing else."""
+        its noise-table sibling and nothing else.  guidance_rescale > 0 (`phi`) swaps it for the factor launches and the
+        scaled step, which always reads the 6-column table (cn = 0 rows and no noise pointer at eta = 0)."""
         noisy = check_eta(kind, eta)
+        phi = float(guidance_rescale) if check_rescale(guidance_rescale) else 0.0
         vpred = self.cfg.ddpm.prediction_type == "v_prediction"
         self._seed(latents)
         if noisy:
             self._load_step_noise(step_noise, len(ts))
         rows = [coefficient_row(kind, self.ac, ts, i, eta) for i in range(len(ts))]
+        if phi:
+            self._ensure_rescale()
         if use_graph:
-            table = self.coef_table6 if noisy else self.coef_table
+            table = self.coef_table6 if noisy or phi else self.coef_table
             table[: len(ts)].copy_(torch.tensor([r[: table.shape[1]] for r in rows], dtype=torch.float32))
             self.ts_table[: len(ts)].copy_(torch.tensor(ts, dtype=torch.int64))
             self.step_idx.zero_()
-            key = (guidance_scale, vpred, noisy)  # eta itself lives in the table: one graph serves every eta > 0
+            # eta itself lives in the table: one graph serves every eta > 0.  phi is a by-value argument of the factor
+            # launch like guidance_scale, so it is part of the key; phi = 0 keeps the key it always had
+            key = (guidance_scale, vpred, noisy) + ((phi,) if phi else ())
             if key not in self._graphs:
-                self._graphs = {k: g for k, g in self._graphs.items() if k[2] != noisy}
-                self._graphs[key] = self._capture(guidance_scale, vpred, noisy)
+                self._graphs = {k: g for k, g in self._graphs.items() if (k[2], len(k)) != (noisy, len(key))}
+                self._graphs[key] = self._capture(guidance_scale, vpred, noisy, phi)
                 self.step_idx.zero_()
                 self._seed(latents)
             for _ in ts:
@@ -307,7 +344,13 @@ class InferenceEngine:
             for i, t in enumerate(ts):
                 conditioning(i, t)
                 self.unet.forward()
-                if noisy:
+                if phi:
+                    ops.cfg_rescale_factor(self.unet.pred, self.rescale_factor, self.rescale_ws, B, self.Lc, n,
+                                           guidance_scale, phi)
+                    ops.cfg_sampler_step_scaled(self.unet.pred, self.x, self.m_prev, self.unet.x_in,
+                                                self.noise_table[i] if noisy else None, self.rescale_factor, B, self.Lc, n,
+                                                guidance_scale, *rows[i], vpred)
+                elif noisy:
                     ops.cfg_sampler_step_noise(self.unet.pred, self.x, self.m_prev, self.unet.x_in, self.noise_table[i], B,
                                                self.Lc, n, guidance_scale, *rows[i], vpred)
                 else:
@@ -361,12 +404,13 @@ class InferenceEngine:
     @torch.no_grad()
     def generate_from_contexts(self, latents: torch.Tensor, prompt_embeds, num_inference_steps: int = 50,
                                guidance_scale: float = 7.5, kind: str = "dpm++2m", decode: bool = True,
-                               eta: float = 0.0, step_noise: Optional[torch.Tensor] = None):
+                               eta: float = 0.0, step_noise: Optional[torch.Tensor] = None,
+                               guidance_rescale: float = 0.0, timestep_spacing: Optional[str] = None):
         """`sd_pipeline_call` with the conditioning ALREADY computed, exactly as the reference passes it
         (sd_pipeline_call.py:86: `prompt_embeds[i] if type(prompt_embeds) == list else prompt_embeds`): a list of T
         per-step XTI dicts (PromptManager.embed_prompt's return value, prompt_manager.py:79-99), one dict, or one tensor.
         The engine's own text pass is skipped; the negative prompt must have been set (set_negative_prompt)."""
-        ts = self._timesteps(kind, num_inference_steps, guidance_scale)
+        ts = self._timesteps(kind, num_inference_steps, guidance_scale, timestep_spacing)
         per_step = type(prompt_embeds) == list
         if per_step and len(prompt_embeds) < len(ts):
             raise ValueError(f"{len(prompt_embeds)} per-step prompt embeddings for {len(ts)} sampler steps")
@@ -378,7 +422,15 @@ class InferenceEngine:
                 self.load_contexts(prompt_embeds[i])
             self.unet.timesteps.fill_(t)
 
-        return self._sample(latents, ts, guidance_scale, kind, decode, eta, step_noise, conditioning, use_graph=False)
+        return self._sample(latents, ts, guidance_scale, kind, decode, eta, step_noise, conditioning, use_graph=False,
+                            guidance_rescale=guidance_rescale)
+
+    # ------------------------------------------------------------------ guidance rescale (phi > 0)
+    def _ensure_rescale(self) -> None:
+        if self.rescale_factor is None:
+            self.rescale_factor = torch.ones(self.B, dtype=torch.float32, device=self.dev)
+            self.rescale_ws = torch.zeros(ops.cfg_rescale_ws_doubles(self.B, self.h * self.w), dtype=torch.float64,
+                                          device=self.dev)
 
     # ------------------------------------------------------------------ stochastic DDIM (eta > 0)
     def _load_step_noise(self, step_noise: Optional[torch.Tensor], T: int) -> None:
@@ -401,7 +453,7 @@ class InferenceEngine:
         self.unet.x_in[:B].copy_(self.x)
         self.unet.x_in[B:].copy_(self.x)
 
-    def _one_step(self, guidance_scale, vpred, noise=False):
+    def _one_step(self, guidance_scale, vpred, noise=False, phi=0.0):
         B, L = self.B, self.L
         ops.table_fill_i64(self.t_text, self.ts_table, self.step_idx)
         ops.table_fill_i64(self.unet.timesteps, self.ts_table, self.step_idx)
@@ -409,7 +461,14 @@ class InferenceEngine:
         self.unet.ctx_k[:, B * L:].copy_(self.ctx_k)
         self.unet.ctx_v[:, B * L:].copy_(self.ctx_v)
         self.unet.forward()
-        if noise:
+        if phi:
+            ops.cfg_rescale_factor(self.unet.pred, self.rescale_factor, self.rescale_ws, B, self.Lc, self.h * self.w,
+                                   guidance_scale, phi)
+            ops.cfg_sampler_step_scaled_table(self.unet.pred, self.x, self.m_prev, self.unet.x_in, B, self.Lc,
+                                              self.h * self.w, guidance_scale, self.coef_table6,
+                                              self.noise_table if noise else None, self.rescale_factor, self.step_idx,
+                                              vpred)
+        elif noise:
             ops.cfg_sampler_step_noise_table(self.unet.pred, self.x, self.m_prev, self.unet.x_in, B, self.Lc,
                                              self.h * self.w, guidance_scale, self.coef_table6, self.noise_table,
                                              self.step_idx, vpred)
@@ -418,11 +477,12 @@ class InferenceEngine:
                                        guidance_scale, self.coef_table, self.step_idx, vpred)
         ops.counter_advance(self.step_idx)
 
-    def _capture(self, guidance_scale, vpred, noise=False):
+    def _capture(self, guidance_scale, vpred, noise=False, phi=0.0):
         """one sampler step as a graph (its warm-up run is a real step: the caller re-seeds x afterwards)"""
-        step = partial(self._one_step, guidance_scale, vpred, noise)
+        step = partial(self._one_step, guidance_scale, vpred, noise, phi)
         return capture_graphs([step], warmup=step)[0]
 
     def memory_bytes(self) -> int:
         noise = 0 if self.noise_table is None else self.noise_table.numel() * 4
-        return self.unet.bytes + self.text.bytes + self.decoder.bytes + noise
+        rescale = 0 if self.rescale_factor is None else self.rescale_factor.numel() * 4 + self.rescale_ws.numel() * 8
+        return self.unet.bytes + self.text.bytes + self.decoder.bytes + noise + rescale

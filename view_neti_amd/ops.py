@@ -317,6 +317,35 @@ def cfg_sampler_step_noise_table(pred, x, m_prev, x_in, Bn, Lc, HW, guidance, co
             _p(coef_table), _p(noise_table), _p(step), 1 if v_prediction else 0, stream())
 
 
+def cfg_rescale_ws_doubles(Bn, HW):
+    n = _l.query("cfg_rescale_ws_doubles", Bn, HW)
+    if n < 0:
+        raise RuntimeError(f"cfg_rescale_factor: unsupported shape Bn={Bn} HW={HW}")
+    return n
+
+
+def cfg_rescale_factor(pred, factor, ws, Bn, Lc, HW, guidance, rescale):
+    """factor[b] = rescale * std(cond[b]) / std(guided[b]) + 1 - rescale (guidance rescale); ws: f64 scratch"""
+    assert factor is None or (factor.dtype == torch.float32 and factor.numel() >= Bn)
+    assert ws is None or Bn <= 0 or HW <= 0 or (ws.dtype == torch.float64 and ws.numel() >= cfg_rescale_ws_doubles(Bn, HW)), \
+        "cfg_rescale_factor: workspace too small"
+    _l.call("cfg_rescale_factor", _p(pred), _ld(pred), _p(factor), _p(ws), Bn, Lc, HW, guidance, rescale, stream())
+
+
+def cfg_sampler_step_scaled(pred, x, m_prev, x_in, noise, factor, Bn, Lc, HW, guidance, alpha_t, sigma_t, cx, c0, c1, cn,
+                            v_prediction):
+    """cfg_sampler_step_noise on the guided prediction times factor[b]; noise may be None (no noise term, cn ignored)"""
+    _l.call("cfg_sampler_step_scaled", _p(pred), _ld(pred), _p(x), _p(m_prev), _p(x_in), _p(noise), _p(factor), Bn, Lc, HW,
+            guidance, alpha_t, sigma_t, cx, c0, c1, cn, 1 if v_prediction else 0, stream())
+
+
+def cfg_sampler_step_scaled_table(pred, x, m_prev, x_in, Bn, Lc, HW, guidance, coef_table, noise_table, factor, step,
+                                  v_prediction):
+    """coef_table: f32 [T][6]; noise_table: f32 [T][B][Lc][HW] or None; factor: f32 [B]; row step[0] of both tables"""
+    _l.call("cfg_sampler_step_scaled_table", _p(pred), _ld(pred), _p(x), _p(m_prev), _p(x_in), Bn, Lc, HW, guidance,
+            _p(coef_table), _p(noise_table), _p(factor), _p(step), 1 if v_prediction else 0, stream())
+
+
 def table_fill_i64(dst, table, step):
     _l.call("table_fill_i64", _p(dst), dst.numel(), _p(table), _p(step), stream())
 
