@@ -438,6 +438,38 @@ int vneti_mse_loss_grad_snr(const void* pred, long long ldp, const float* target
 int vneti_mse_loss_per_sample(const void* pred, long long ldp, const float* target, float* out, float* ws, int Bn, int Lc,
                               int HW, void* stream);
 long long vneti_mse_loss_per_sample_ws_floats(int Bn, int HW);
+/* Object-masked diffusion loss (extension: data.mask_dir).  The reference has no such option; the
+ * form is that of the per-pixel loss weights of kohya's masked loss and Break-A-Scene, normalised per sample the way
+ * compat/dtu_metrics.py normalises its masked MSE.  NO QUALITY CLAIM is attached to it.
+ *
+ * vneti_loss_weights_from_mask: one row of the weight table from one uint8 mask image of H x W pixels, pixel_stride 1 or
+ * 3 bytes (channel 0 is read; 3 is what the device input pipeline leaves behind).  f: the VAE's down-sampling factor
+ * (H % f == 0 and W % f == 0, else refused); h = H / f, w = W / f.  Per latent cell p, in f64 from integer counts:
+ *   cnt_p = #{pixels of the cell >= threshold};      m_p = background + (1 - background) cnt_p / f^2
+ *   norm = sum_p m_p = background h w + (1 - background) (sum_p cnt_p) / f^2   (the integer sum is exact)
+ *   q_row[p] = (float)(m_p (h w / norm)),  rounded once;  norm == 0 (empty mask, background 0): a row of exact zeros
+ * so mean_p q = 1, and a mask that is foreground everywhere gives q == 1.0f exactly whatever the background weight.
+ * threshold in 0..255 (3 is `mask / 255 > 0.01`), background in [0, 1].  Deterministic: two launches, integer partial sums,
+ * no float atomics; q_row depends on the mask and (H, W, f, threshold, background) only.  ws: scratch of
+ * vneti_loss_weights_from_mask_ws_ints(H, W, f) int32 (negative: refused shape).  The mask stays under 2 GiB. */
+int vneti_loss_weights_from_mask(const void* mask_u8, int H, int W, int pixel_stride, int f, int threshold,
+                                 float background, float* q_row, int* ws, void* stream);
+long long vneti_loss_weights_from_mask_ws_ints(int H, int W, int f);
+/* vneti_mse_loss_grad_snr with one more operand, q: f32 [Bn][HW] (rows of vneti_loss_weights_from_mask), and a null-able
+ * (timesteps, alphas_cumprod) pair — both null: no Min-SNR factor, w_b = 1 and gamma / v_prediction are ignored.
+ *   loss_sum += sum (pred - target)^2 (w_b q_bp);   dpred = 2 (pred - target) (w_b q_bp) / N * loss_scale[0],  N = Bn Lc HW
+ * so loss_sum / N = mean_b[ w_b sum_{c,p} m_bp d^2 / (Lc sum_p m_bp) ]: every sample is normalised by its own mask mass.
+ * One launch, as the two entries above.  q == 1.0f gives their dpred bit for bit (vneti_mse_loss_grad with the null pair,
+ * vneti_mse_loss_grad_snr with it).  pred and dpred each stay under 2 GiB. */
+int vneti_mse_loss_grad_weighted(const void* pred, long long ldp, const float* target, void* dpred, long long lddp,
+                                 float* loss_sum, const float* loss_scale, const float* q, int Bn, int Lc, int HW,
+                                 const void* timesteps_i64, const float* alphas_cumprod, float gamma, int v_prediction,
+                                 void* stream);
+/* vneti_mse_loss_per_sample with q (f32 [Bn][HW]): out[b] = sum_{c,p} q_bp (pred - target)^2 / (Lc HW).  The same fixed-order
+ * two-stage reduction, the same workspace query, the same independence of Bn and b; q == 1.0f gives the unweighted
+ * entry's out bit for bit. */
+int vneti_mse_loss_per_sample_weighted(const void* pred, long long ldp, const float* target, const float* q, float* out,
+                                       float* ws, int Bn, int Lc, int HW, void* stream);
 /* torch.optim.AdamW over one flat f32 bucket with torch.cuda.amp.GradScaler semantics
  * (training/coach.py:214-218,750-756).  hyper = {lr, beta1, beta2, eps, weight_decay, grad_div};
  * scaler = {loss_scale, growth_tracker, found_inf}; step = int32 optimizer step count.

@@ -5,6 +5,7 @@ engine for all iterations.
     python scripts/heldout_loss.py --input_dir <run> --iterations [1500,3000] \
         [--heldout_loss_timesteps 4] [--heldout_loss_seed 0] [--eval_placeholder_object_tokens ["<scan65>"]] \
         [--use_ema true]   (the averaged mappers mapper-ema-steps-N_* of a run with optim.ema_decay)
+        [--heldout_loss_masked true]   ("loss_masked" beside every loss: the run's data.mask_dir object masks)
 
 Appends one line per iteration to <run>/heldout-loss-offline.jsonl and prints iteration x train / test.
 """
@@ -27,6 +28,7 @@ class HeldoutLossConfig:
     heldout_loss_timesteps: int = 4
     heldout_loss_seed: int = 0
     use_ema: bool = False
+    heldout_loss_masked: bool = False
 
 
 def main(args=None):
@@ -35,7 +37,8 @@ def main(args=None):
         raise SystemExit("heldout_loss: --input_dir and --iterations are required")
     from view_neti_amd.compat import heldout
     records = heldout.offline(cfg.input_dir, cfg.iterations, cfg.eval_placeholder_object_tokens,
-                              cfg.heldout_loss_timesteps, cfg.heldout_loss_seed, use_ema=cfg.use_ema)
+                              cfg.heldout_loss_timesteps, cfg.heldout_loss_seed, use_ema=cfg.use_ema,
+                              masked=cfg.heldout_loss_masked)
     print(heldout.format_table(records))
     return records
 

@@ -196,6 +196,13 @@ def draw_plan(key: int, size: Tuple[int, int], width: int, height: int) -> List[
     return plan
 
 
+def geometric_plan(plan: List[tuple]) -> List[tuple]:
+    """the operations of a drawn plan that move pixels — `rotate` and `rrcrop`, in the plan's order — without the ones that
+    only recolour them (jitter, gray, blur): what an object mask goes through beside its image (applied with
+    fill=0, so what a rotation brings in is background)"""
+    return [op for op in plan if op[0] in ("rotate", "rrcrop")]
+
+
 def apply_plan(img: Image.Image, plan: List[tuple], fill: int = 1) -> Image.Image:
     for op in plan:
         kind = op[0]

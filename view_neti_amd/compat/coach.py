@@ -133,6 +133,8 @@ class Coach:
             max_grad_norm=None if forward_only else cfg.optim.max_grad_norm,
             snr_gamma=None if forward_only else cfg.optim.snr_gamma,
             noise_offset=None if forward_only else cfg.optim.noise_offset,
+            loss_mask=cfg.data.mask_dir is not None and not forward_only,
+            loss_mask_background=0.0 if forward_only else cfg.optim.loss_mask_background,
             **({} if forward_only else self._ema_kwargs()),
             telemetry_rows=self._telemetry_rows(), **first.engine_encoder_kwargs(), **kw)
         # per-step record (extension): every rank records (one launch list for all), rank 0 writes the file
@@ -239,7 +241,8 @@ class Coach:
         return resume.fingerprint(cfg.learnable_mode, cfg.optim.train_batch_size, cfg.optim.gradient_accumulation_steps,
                                   self.world, cfg.optim.mixed_precision, cfg.seed, len(self.train_dataset), n_params,
                                   max_grad_norm=cfg.optim.max_grad_norm, snr_gamma=cfg.optim.snr_gamma,
-                                  noise_offset=cfg.optim.noise_offset, **self._ema_kwargs())
+                                  noise_offset=cfg.optim.noise_offset, loss_mask=cfg.data.mask_dir is not None,
+                                  loss_mask_background=cfg.optim.loss_mask_background, **self._ema_kwargs())
 
     def _ema_kwargs(self) -> Dict:
         """optim.ema_* as the training engine and the resume fingerprint take them"""
@@ -271,6 +274,8 @@ class Coach:
                 self._ac_host = self.engine.ac.cpu().numpy()
             snr = dict(snr_gamma=self.engine.snr_gamma, alphas_cumprod=self._ac_host,
                        v_prediction=self.engine.cfg.ddpm.prediction_type == "v_prediction")
+        if self.engine.loss_weights is not None:  # the recorded per-sample losses are the masked ones
+            snr["masked"] = True
         self.metrics.append(lines_up_to(groups, global_step, omit_object=self.mapper_object_lookup is None, **snr))
 
     def _load_resume_mappers(self, directory=None, step: Optional[int] = None, files=None):
@@ -358,6 +363,24 @@ class Coach:
             pipe.run(src, self.engine.pixel_values[b], resize=ds.target_size(), flip=a["flip"], plan=a["plan"])
         return None
 
+    def _loss_masks(self, batch):
+        """data.mask_dir: the batch's object masks into the engine's weight table, outside the captured
+        step.  Host path: the collated uint8 masks through the pinned stager.  Device path: the mask source cached in HBM
+        beside the image, through the geometric part of the image's plan with fill 0, straight into the preparation entry"""
+        if self.engine.loss_weights is None:
+            return
+        if "aug" not in batch:
+            self.engine.set_loss_masks(batch["loss_mask"])
+            return
+        from .augment import geometric_plan
+        ds, pipe = self.train_dataset, self.device_pipe
+        for b, a in enumerate(batch["aug"]):
+            src = self._device_sources.get(a["mask_path"])
+            if src is None:
+                src = self._device_sources[a["mask_path"]] = pipe.upload(ds.load_source(a["mask_path"]))
+            img, h, w = pipe.run(src, None, resize=ds.target_size(), flip=a["flip"], plan=geometric_plan(a["plan"]), fill=0)
+            self.engine.set_loss_mask(b, img, h, w, 3)
+
     # ------------------------------------------------------------------ set-up
     def _setup_logging(self):
         cfg = self.cfg
@@ -400,7 +423,8 @@ class Coach:
             fixed_object_token_or_path=d.fixed_object_token_or_path, dtu_lighting=d.dtu_lighting,
             dtu_subset=d.dtu_subset, caption_strategy=d.caption_strategy, dtu_preprocess_key=d.dtu_preprocess_key,
             augmentation_key=d.augmentation_key,  # flip_p is NOT forwarded — reference quirk Q10
-            device_pipeline=bool(getattr(d, "device_input_pipeline", False)))
+            device_pipeline=bool(getattr(d, "device_input_pipeline", False)),
+            **({} if d.mask_dir is None else {"mask_dir": d.mask_dir}))
 
     def _add_concept_tokens(self):
         ds, tok = self.train_dataset, self.tokenizer
@@ -585,6 +609,7 @@ class Coach:
                               self._view_params(batch["input_ids_placeholder_view"]),
                               object_index=self.object_slot.get(int(ids_obj[0]), 0),  # (-1 in mode 1: no object mapper)
                               image_idx=batch["image_idx"] if eng.n_cache else None)
+                self._loss_masks(batch)
                 if not captured:
                     eng.capture()
                     captured = True

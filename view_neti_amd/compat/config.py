@@ -90,6 +90,12 @@ class DataConfig:
     # sample — of an image is the same every time it comes up: keep them in HBM (64 KiB per 512^2 image) and re-draw only
     # `.sample()`.  Bit-identical training; the VAE encoder runs once per image instead of once per step.
     cache_vae_moments: bool = field(default=False, metadata={"ext": True})
+    # extension: a folder of object masks; setting it weights the training loss per latent pixel by the
+    # sample's mask (optim.loss_mask_background is the weight of the background).  DTU roots: the lookup of
+    # dtu_metrics.get_object_masks, `<mask_dir>/scanN[/mask]/NNN.png` by camera index; any other root:
+    # `<mask_dir>/<image stem>.png`.  A training image without a mask file is an error.  Same rules as optim.max_grad_norm:
+    # it describes the trained model, named only where set
+    mask_dir: Optional[Path] = field(default=None, metadata={"ext": True, "when_set": True})
     # filled at run time; a plain class attribute (NOT a dataclass field) as in the reference (config.py:64), so it
     # never enters config.yaml / the checkpoint's cfg dict
     placeholder_view_tokens = None
@@ -194,6 +200,9 @@ class EvalConfig:
     # [0, 1] and the schedulers' timestep_spacing (None | "trailing").  They touch no training step.
     guidance_rescale: float = field(default=0.0, metadata={"ext": True, "run_control": True})
     timestep_spacing: Optional[str] = field(default=None, metadata={"ext": True, "run_control": True})
+    # a "loss_masked" value beside every held-out loss: the same residual under the evaluation view's object mask at the
+    # training resolution.  Needs data.mask_dir
+    heldout_loss_masked: bool = field(default=False, metadata={"ext": True, "run_control": True})
     # plain class attribute in the reference too (config.py:188)
     validation_view_tokens = None
 
@@ -244,8 +253,13 @@ class OptimConfig:
     ema_decay: Optional[float] = field(default=None, metadata={"ext": True, "when_set": True})
     ema_update_after_step: int = field(default=0, metadata={"ext": True, "when_set": True})
     ema_warmup_power: Optional[float] = field(default=None, metadata={"ext": True, "when_set": True})
+    # extension: the weight of a background pixel in the object-masked loss that data.mask_dir turns on, in
+    # [0, 1] (0: the background carries no gradient; 1: the plain loss).  Same rules as max_grad_norm
+    loss_mask_background: float = field(default=0.0, metadata={"ext": True, "when_set": True})
 
     def __post_init__(self):
+        if not 0.0 <= self.loss_mask_background <= 1.0:
+            raise ValueError(f"optim.loss_mask_background must lie in [0, 1] (is {self.loss_mask_background})")
         if self.ema_decay is not None and not 0.0 < self.ema_decay < 1.0:
             raise ValueError(f"optim.ema_decay must be in (0, 1) when set (is {self.ema_decay})")
         if self.ema_warmup_power is not None and not 0.0 < self.ema_warmup_power < float("inf"):
@@ -285,6 +299,10 @@ class RunConfig:
         if self.data.placeholder_object_tokens is not None:
             assert len(self.data.placeholder_object_tokens) == len(set(self.data.placeholder_object_tokens)), \
                 "cfg.data.placeholder_object_tokens must be unique strings"
+        if self.optim.loss_mask_background != 0.0 and self.data.mask_dir is None:
+            raise ValueError("optim.loss_mask_background needs data.mask_dir")
+        if self.eval.heldout_loss_masked and self.data.mask_dir is None:
+            raise ValueError("eval.heldout_loss_masked needs data.mask_dir")
         if self.learnable_mode in (4, 5):
             assert self.model.pretrained_view_mapper or self.model.pretrained_view_mapper_key
             if self.model.pretrained_view_mapper_key:

@@ -30,8 +30,9 @@ class TextualInversionDataset(torch.utils.data.Dataset):
                  fixed_object_token_or_path=None, size: int = 512, repeats: int = 100, flip_p: float = 0.0,
                  set: str = "train", placeholder_object_token: str = "*", dtu_lighting: str = "3", dtu_subset: int = 0,
                  caption_strategy: int = 0, dtu_preprocess_key: int = 0, augmentation_key: int = 0,
-                 center_crop: bool = False, device_pipeline: bool = False):
+                 center_crop: bool = False, device_pipeline: bool = False, mask_dir: Optional[Path] = None):
         self.learnable_mode = learnable_mode
+        self.mask_dir = None if mask_dir is None else Path(mask_dir)  # object masks of the training images
         self.device_pipeline = device_pipeline  # images are produced on the GPU from the plan this dataset draws
         self.data_root = Path(data_root)
         self.tokenizer = tokenizer
@@ -103,6 +104,17 @@ class TextualInversionDataset(torch.utils.data.Dataset):
             else:
                 self.placeholder_object_tokens = [placeholder_object_token]
         self.placeholder_tokens = self.placeholder_view_tokens + self.placeholder_object_tokens
+        if self.mask_dir is not None:
+            # every training image has its mask, on the image's own pixel grid: checked now (headers only), so that a
+            # missing file stops the run at its construction and is never "fully foreground in silence"
+            for f in self.image_paths_flattened:
+                m = self.mask_path(f)
+                if not m.is_file():
+                    raise FileNotFoundError(f"data.mask_dir: no object mask for the training image {f} (expected {m})")
+                with Image.open(m) as mi, Image.open(f) as ii:
+                    if mi.size != ii.size:
+                        raise ValueError(f"data.mask_dir: {m} is {mi.size[0]}x{mi.size[1]}, its image {f} is "
+                                         f"{ii.size[0]}x{ii.size[1]}: a mask lies on its image's pixel grid")
 
     # ------------------------------------------------------------------ DTU helpers (dataset.py:320-522)
     @staticmethod
@@ -220,6 +232,35 @@ class TextualInversionDataset(torch.utils.data.Dataset):
             arr = np.concatenate([arr, np.zeros((400, arr.shape[1], 3), np.uint8)], 0)
         return arr
 
+    # ------------------------------------------------------------------ object masks
+    def mask_path(self, image_path) -> Path:
+        """the mask file of a training (or evaluation) image under `mask_dir`.  DTU roots: the lookup of
+        dtu_metrics.get_object_masks, `<mask_dir>/scanN[/mask]/NNN.png` with the scan of the image's own folder (mode 3: the
+        scene being sampled) and NNN the 0-based camera index; any other root: `<mask_dir>/<image stem>.png`.  "DTU root" is this
+        class's one predicate, the reference's (dataset.py:155-236): the string "dtu" in the data root's path, as `_resize`,
+        `target_size` and `load_source` decide it — so a data set of another kind under a path that contains "dtu" is
+        treated as DTU by all four, and here raises unless its images lie in `scanN` folders"""
+        image_path = Path(image_path)
+        if "dtu" in str(self.data_root):
+            scan = image_path.parent.name
+            if not (scan.startswith("scan") and scan[4:].isdigit()):
+                raise ValueError(f"data.mask_dir: cannot tell the DTU scan of {image_path} (its folder is not `scanN`)")
+            scan_dir = self.mask_dir / scan
+            folder = scan_dir / "mask" if (scan_dir / "mask").exists() else scan_dir
+            return folder / f"{self.dtu_cam_info_from_fname(image_path)[0]:03d}.png"
+        return self.mask_dir / f"{image_path.stem}.png"
+
+    def load_mask(self, image_path, flip: bool = False, plan=None) -> np.ndarray:
+        """the mask of `image_path` through the image's geometry and nothing else — load_source, the bicubic `_resize`, the
+        flip, and the rotate / rrcrop operations of the image's drawn `plan` with fill 0 — as uint8 (H, W), channel 0.  It
+        is binarised where it is used (value >= 3, `mask / 255 > 0.01`)"""
+        from .augment import apply_plan, geometric_plan
+        image = self._resize(Image.fromarray(self.load_source(self.mask_path(image_path))))
+        if flip:
+            image = image.transpose(Image.FLIP_LEFT_RIGHT)
+        image = apply_plan(image, geometric_plan(plan or []), fill=0)
+        return np.ascontiguousarray(np.array(image).astype(np.uint8)[:, :, 0])
+
     def load_pixels(self, path) -> torch.Tensor:
         """the deterministic part of __getitem__'s image path — RGB, centre crop, `_resize`, [-1, 1] as (3, H, W) f32 —
         without flip or augmentation and without a random draw (held-out evaluation, compat/heldout.py)"""
@@ -283,8 +324,27 @@ class TextualInversionDataset(torch.utils.data.Dataset):
                 tgt = self.target_size() or self._source_hw(image.size[::-1])
                 plan = draw_plan(self.augmentation_key, self.aug_size, tgt[1], tgt[0])
             ex["aug"] = dict(path=str(path), flip=flip, plan=plan)
+            if self.mask_dir is not None:  # (the device executes the plan's geometric part on the cached mask)
+                ex["aug"]["mask_path"] = str(self.mask_path(path))
             return ex
         image = self._resize(Image.fromarray(self._source_array(image)))
+        if self.mask_dir is not None:
+            # the same draws in the same order as below, with the plan in hand: the image gets all of it, the mask its
+            # geometric part
+            from .augment import apply_plan, draw_plan
+            flip = bool(self.learnable_mode == 0 and self.flip_p > 0 and torch.rand(1).item() < self.flip_p)
+            if flip:
+                image = image.transpose(Image.FLIP_LEFT_RIGHT)
+            plan = []
+            if self.augmentations is not None:
+                img_size = image.size
+                plan = draw_plan(self.augmentation_key, self.aug_size, image.size[0], image.size[1])
+                image = apply_plan(image, plan)
+                assert image.size == img_size  # dataset.py:731-732
+            arr = (np.array(image).astype(np.uint8) / 127.5 - 1.0).astype(np.float32)
+            ex["pixel_values"] = torch.from_numpy(arr).permute(2, 0, 1)
+            ex["loss_mask"] = torch.from_numpy(self.load_mask(path, flip, plan))
+            return ex
         if self.learnable_mode == 0 and self.flip_p > 0 and torch.rand(1).item() < self.flip_p:
             image = image.transpose(Image.FLIP_LEFT_RIGHT)
         if self.augmentations is not None:

@@ -108,16 +108,24 @@ def _object_record(p: Plan, rows: List[Tuple[Item, float]]) -> dict:
 
 
 def make_record(step: int, p: Plan, losses: Dict[Optional[str], List[Tuple[Item, float]]],
-                ema_losses: Optional[Dict[Optional[str], List[Tuple[Item, float]]]] = None) -> dict:
+                ema_losses: Optional[Dict[Optional[str], List[Tuple[Item, float]]]] = None,
+                masked_losses: Optional[Dict[Optional[str], List[Tuple[Item, float]]]] = None) -> dict:
     """{"step", "timesteps", "objects": {tok: {"train", "test", "by_timestep": {t: {"train", "test"}}, "by_view": {cam: m}}}};
     every m is a mean over per-sample losses, None for an empty split.  ema_losses (a run with optim.ema_decay): the same
     plan evaluated with the averaged mappers; each object then gains "ema": {"train", "test", "by_timestep", "by_view"}
-    beside the unchanged raw fields"""
+    beside the unchanged raw fields.  masked_losses (eval.heldout_loss_masked): the same items' losses under
+    the evaluation views' object masks; each object then gains "loss_masked": the four fields again, and "by_view_timestep":
+    {cam: {t: value}}, one value per (camera, timestep)"""
     objects = {}
     for obj, rows in losses.items():
         objects[str(obj)] = _object_record(p, rows)
         if ema_losses is not None:
             objects[str(obj)]["ema"] = _object_record(p, ema_losses[obj])
+        if masked_losses is not None:
+            m = _object_record(p, masked_losses[obj])
+            m["by_view_timestep"] = {str(c): {str(it.timestep): v for it, v in masked_losses[obj] if it.cam == c}
+                                     for c in p.cams}
+            objects[str(obj)]["loss_masked"] = m
     return {"step": int(step), "timesteps": list(p.timesteps), "objects": objects}
 
 
@@ -137,9 +145,13 @@ def read_records(path) -> List[dict]:
             for o in r["objects"].values():
                 o["by_timestep"] = {int(t): v for t, v in o["by_timestep"].items()}
                 o["by_view"] = {int(c): v for c, v in o["by_view"].items()}
-                if "ema" in o:
-                    o["ema"]["by_timestep"] = {int(t): v for t, v in o["ema"]["by_timestep"].items()}
-                    o["ema"]["by_view"] = {int(c): v for c, v in o["ema"]["by_view"].items()}
+                for sub in ("ema", "loss_masked"):
+                    if sub in o:
+                        o[sub]["by_timestep"] = {int(t): v for t, v in o[sub]["by_timestep"].items()}
+                        o[sub]["by_view"] = {int(c): v for c, v in o[sub]["by_view"].items()}
+                if "loss_masked" in o:
+                    o["loss_masked"]["by_view_timestep"] = {int(c): {int(t): v for t, v in d.items()}
+                                                            for c, d in o["loss_masked"]["by_view_timestep"].items()}
             out.append(r)
     return out
 
@@ -156,7 +168,9 @@ class HeldoutLoss:
     """Built by a Coach (rank 0).  Reads the Coach's dataset, tokenizer, camera scaling and engine; the preprocessed
     pixels of the evaluation images and the fixed noise are prepared at the first evaluation and kept."""
 
-    def __init__(self, coach, n_timesteps: Optional[int] = None, seed: Optional[int] = None):
+    masked = False  # (eval.heldout_loss_masked, set by __init__)
+
+    def __init__(self, coach, n_timesteps: Optional[int] = None, seed: Optional[int] = None, masked: Optional[bool] = None):
         from .inference_dtu import eval_object_token, scene_of
         self.coach = coach
         cfg, ds, eng = coach.cfg, coach.train_dataset, coach.engine
@@ -188,6 +202,18 @@ class HeldoutLoss:
                 if not f.is_file():
                     raise FileNotFoundError(f"held-out loss: the evaluation image of camera {cam} ({obj}) is missing: {f}")
                 self.image_path[(obj, cam)] = f
+        # eval.heldout_loss_masked: the evaluation views' object masks at the training resolution; a
+        # missing mask file stops the run here as well
+        self.masked = bool(cfg.eval.heldout_loss_masked if masked is None else masked)
+        self._mask_rows: Dict[Tuple[Optional[str], int], torch.Tensor] = {}
+        if self.masked:
+            if ds.mask_dir is None:
+                raise ValueError("the masked held-out loss needs data.mask_dir")
+            for key, f in self.image_path.items():
+                if not ds.mask_path(f).is_file():
+                    raise FileNotFoundError(f"held-out loss: the object mask of camera {key[1]} ({key[0]}) is missing: "
+                                            f"{ds.mask_path(f)}")
+            self._weights = torch.ones(eng.B, eng.h * eng.w, dtype=torch.float32, device=eng.dev)
         self._pixels: Dict[Tuple[Optional[str], int], torch.Tensor] = {}
         self._noise: Dict[Tuple[int, int], Tuple[torch.Tensor, torch.Tensor]] = {}
         self._text: Dict[Optional[str], Tuple[torch.Tensor, int, int]] = {}
@@ -203,6 +229,25 @@ class HeldoutLoss:
                                  f"{tuple(self.coach.engine.pixel_values.shape[2:])}")
             self._pixels[key] = px
         return self._pixels[key]
+
+    def mask_row(self, obj, cam) -> torch.Tensor:
+        """the loss weights of one evaluation view (f32 device [h*w]): its mask through load_source and `_resize`, no flip,
+        no augmentation, then the preparation entry with the run's background weight"""
+        from .. import ops
+        key = (obj, cam)
+        if key not in self._mask_rows:
+            eng, ds = self.coach.engine, self.coach.train_dataset
+            m = torch.from_numpy(ds.load_mask(self.image_path[key])).to(eng.dev)
+            if tuple(m.shape) != (eng.H, eng.W):
+                raise ValueError(f"{ds.mask_path(self.image_path[key])}: preprocessed to {tuple(m.shape)}, the engine trains "
+                                 f"at {(eng.H, eng.W)}")
+            row = torch.empty(1, eng.h * eng.w, dtype=torch.float32, device=eng.dev)
+            ws = torch.zeros(ops.loss_weights_from_mask_ws_ints(eng.H, eng.W, eng.vae_factor), dtype=torch.int32,
+                             device=eng.dev)
+            ops.loss_weights_from_mask(m, eng.H, eng.W, 1, eng.vae_factor, eng.MASK_THRESHOLD,
+                                       self.coach.cfg.optim.loss_mask_background, row, 0, ws)
+            self._mask_rows[key] = row[0]
+        return self._mask_rows[key]
 
     def noise(self, cam, k) -> Tuple[torch.Tensor, torch.Tensor]:
         if (cam, k) not in self._noise:
@@ -238,7 +283,8 @@ class HeldoutLoss:
         return self._cams[cam]
 
     # -- the evaluation
-    def evaluate(self) -> Dict[Optional[str], List[Tuple[Item, float]]]:
+    def evaluate(self, masked_out: Optional[dict] = None) -> Dict[Optional[str], List[Tuple[Item, float]]]:
+        """masked_out: a dict that receives the masked losses of the same items (only with `masked`)"""
         coach, eng = self.coach, self.coach.engine
         has_view = coach.mapper_view is not None
         out = {}
@@ -246,7 +292,7 @@ class HeldoutLoss:
             ids, po, pv = self.text(obj)
             B = eng.B
             slot = coach.object_slot.get(po, 0)
-            rows = []
+            rows, mrows = [], []
             for items, n in batches:
                 eng.set_batch(torch.stack([self.pixels(obj, it.cam) for it in items]), ids.unsqueeze(0).repeat(B, 1),
                               torch.full((B,), po), torch.full((B,), pv) if has_view else None,
@@ -255,20 +301,28 @@ class HeldoutLoss:
                 pairs = [self.noise(it.cam, it.k) for it in items]
                 eng.set_noise(torch.stack([e for e, _ in pairs]), torch.stack([z for _, z in pairs]),
                               torch.tensor([it.timestep for it in items], dtype=torch.int64))
-                losses = eng.eval_losses().tolist()
+                if masked_out is None:
+                    losses = eng.eval_losses().tolist()
+                else:
+                    torch.stack([self.mask_row(obj, it.cam) for it in items], out=self._weights)
+                    losses, mlosses = (v.tolist() for v in eng.eval_losses(weights=self._weights))
+                    mrows += [(it, mlosses[i]) for i, it in enumerate(items[:n])]
                 rows += [(it, losses[i]) for i, it in enumerate(items[:n])]
             out[obj] = rows
+            if masked_out is not None:
+                masked_out[obj] = mrows
         return out
 
     def run(self, step: int, file_name: str = FILE_NAME, weights: Optional[str] = None) -> dict:
         """one evaluation -> one line.  An engine that keeps an average of the mappers (optim.ema_decay) runs the plan twice,
         raw and then inside ema_weights().  weights: a note of which saved weights the engine holds (offline, --use_ema)"""
-        losses, ema_losses = self.evaluate(), None
+        masked = {} if self.masked else None
+        losses, ema_losses = (self.evaluate() if masked is None else self.evaluate(masked)), None
         eng = self.coach.engine
         if eng.ema is not None:
             with eng.ema_weights():
                 ema_losses = self.evaluate()
-        record = make_record(step, self.plan, losses, ema_losses)
+        record = make_record(step, self.plan, losses, ema_losses, masked)
         if weights is not None:
             record["weights"] = weights
         append_record(Path(self.coach.cfg.log.exp_dir) / file_name, record)
@@ -278,11 +332,13 @@ class HeldoutLoss:
 
 # ---------------------------------------------------------------------------------------------- saved checkpoints
 def offline(input_dir, iterations: Sequence[int], eval_placeholder_object_tokens: Sequence[str] = (),
-            n_timesteps: int = 4, seed: int = 0, device: str = "cuda", use_ema: bool = False) -> List[dict]:
+            n_timesteps: int = 4, seed: int = 0, device: str = "cuda", use_ema: bool = False,
+            masked: bool = False) -> List[dict]:
     """The same plan, seeds and inputs on the `mapper-steps-N` checkpoints of a finished run: the run's config from the
     first checkpoint (`inference_dtu.load_train_cfg`), ONE forward-only engine, each iteration's mappers copied into it
     in place.  Appends to <input_dir>/heldout-loss-offline.jsonl and returns the records.  use_ema: the averaged mappers
-    `mapper-ema-steps-N` of a run with optim.ema_decay instead (a missing file raises); such a line says "weights": "ema"."""
+    `mapper-ema-steps-N` of a run with optim.ema_decay instead (a missing file raises); such a line says "weights": "ema".
+    masked: "loss_masked" beside every loss, under the object masks of the run's data.mask_dir (which it then needs)."""
     from .coach import Coach
     from .inference_dtu import load_train_cfg
     input_dir = Path(input_dir)
@@ -294,7 +350,7 @@ def offline(input_dir, iterations: Sequence[int], eval_placeholder_object_tokens
     if eval_placeholder_object_tokens:
         cfg.eval.eval_placeholder_object_tokens = list(eval_placeholder_object_tokens)
     coach = Coach(cfg, device=device, forward_only=True)
-    ev = HeldoutLoss(coach, n_timesteps=n_timesteps, seed=seed)
+    ev = HeldoutLoss(coach, n_timesteps=n_timesteps, seed=seed, masked=masked)
     records = []
     for it in iterations:
         coach.load_mappers(input_dir, it, ema=use_ema)

@@ -250,7 +250,8 @@ def prune_states(directory, keep: int) -> List[Path]:
 def fingerprint(learnable_mode: int, batch_size: int, grad_accum: int, world: int, precision: str, seed: Optional[int],
                 dataset_len: int, n_params: Optional[int] = None, max_grad_norm: Optional[float] = None,
                 snr_gamma: Optional[float] = None, noise_offset: Optional[float] = None, ema_decay: Optional[float] = None,
-                ema_update_after_step: int = 0, ema_warmup_power: Optional[float] = None) -> Dict[str, Any]:
+                ema_update_after_step: int = 0, ema_warmup_power: Optional[float] = None, loss_mask: bool = False,
+                loss_mask_background: float = 0.0) -> Dict[str, Any]:
     fp = {"learnable_mode": int(learnable_mode), "train_batch_size": int(batch_size),
           "gradient_accumulation_steps": int(grad_accum), "world_size": int(world), "precision": str(precision),
           "seed": -1 if seed is None else int(seed), "dataset_len": int(dataset_len)}
@@ -268,11 +269,16 @@ def fingerprint(learnable_mode: int, batch_size: int, grad_accum: int, world: in
         fp["ema_update_after_step"] = int(ema_update_after_step)
     if ema_warmup_power is not None:
         fp["ema_warmup_power"] = float(ema_warmup_power)
+    if loss_mask:  # (and for the object-masked objective)
+        fp["loss_mask"] = True
+    if loss_mask_background:
+        fp["loss_mask_background"] = float(loss_mask_background)
     return fp
 
 
 # fields that are present only where they are set: absent on one side and present on the other is a difference too
-_WHEN_SET = ("max_grad_norm", "snr_gamma", "noise_offset", "ema_decay", "ema_update_after_step", "ema_warmup_power")
+_WHEN_SET = ("max_grad_norm", "snr_gamma", "noise_offset", "ema_decay", "ema_update_after_step", "ema_warmup_power",
+             "loss_mask", "loss_mask_background")
 
 
 def check_fingerprint(saved: Dict[str, Any], current: Dict[str, Any]):

@@ -13,8 +13,9 @@ fetches the ring where the train loop already syncs; this module turns the rows 
 of `grad_norm` that the run does not train is omitted (mode 1: no object mapper; mode 5: a frozen view mapper); a non-finite
 norm (a skipped step) is null.  A run with `optim.snr_gamma` (§9 f8) has one more key, `"loss_weighted"`: the Min-SNR
 weighted mean of the same samples — the quantity the step minimises — computed here in f64 from the (t, loss) pairs and the
-f32 `alphas_cumprod` table; `loss` stays the unweighted mean, so files of weighted and unweighted runs compare.  Pure
-functions and a small file writer: no GPU."""
+f32 `alphas_cumprod` table; `loss` stays the unweighted mean, so files of weighted and unweighted runs compare.  A run with
+`data.mask_dir` (§9 f11) says `"masked": true`: its per-sample losses, and every mean over them, are the object-masked
+ones.  Pure functions and a small file writer: no GPU."""
 from __future__ import annotations
 
 import json
@@ -58,9 +59,10 @@ def min_snr_weight(alpha_cumprod: float, gamma: float, v_prediction: bool = Fals
 
 def step_line(step: int, group: List[Dict], omit_object: bool = False, omit_view: bool = False,
               snr_gamma: Optional[float] = None, alphas_cumprod: Optional[Sequence[float]] = None,
-              v_prediction: bool = False) -> Dict:
+              v_prediction: bool = False, masked: bool = False) -> Dict:
     """one optimizer step's line from the rows of its accumulation group (the last row closed it).  snr_gamma set: the
-    line gains "loss_weighted" (alphas_cumprod: the f32 table, indexable by timestep)"""
+    line gains "loss_weighted" (alphas_cumprod: the f32 table, indexable by timestep).  masked: the rows' losses are the
+    object-masked ones; the line says "masked": true"""
     last = group[-1]
     assert last["closed"], "the group's last micro-step did not close it"
     samples = [{"t": t, "loss": l} for r in group for t, l in zip(r["timesteps"], r["losses"])]
@@ -75,6 +77,8 @@ def step_line(step: int, group: List[Dict], omit_object: bool = False, omit_view
             raise ValueError("step_line(): snr_gamma needs the alphas_cumprod table")
         w = [min_snr_weight(alphas_cumprod[int(s["t"])], snr_gamma, v_prediction) for s in samples]
         line["loss_weighted"] = finite_or_none(sum(wi * float(s["loss"]) for wi, s in zip(w, samples)) / len(samples))
+    if masked:
+        line["masked"] = True
     return line
 
 

@@ -526,12 +526,16 @@ __global__ void image_postprocess_kernel(const half_t* img, long long ldi, float
 // compute_snr: snr = ac/(1-ac); w = min(snr, gamma)/snr, or /(snr+1) for v-prediction), computed here in f32 —
 // always, also when w is 1 (then it changes no bit).  SNR = false is the body the unweighted entry always had: t, ac,
 // gamma and vpred are never read.
-template <bool SNR>
+// WQ (the _weighted entry): one more factor per latent pixel, q[b][p] (f32 [Bn][HW], the normalised object
+// mask of vneti_loss_weights_from_mask): the term's weight is w_b * q_bp — q_bp alone without SNR — one rounded f32
+// product, also when q is 1 (then it changes no bit against the entry without q).  WQ = false never reads q: the two
+// bodies above are the ones the kernel always had.
+template <bool SNR, bool WQ = false>
 __global__ __launch_bounds__(256) void mse_loss_grad_kernel(const half_t* pred, long long ldp, const float* target,
                                                             half_t* dpred, long long lddp, float* loss_sum,
                                                             const float* loss_scale, int Bn, int Lc, int HW,
                                                             const long long* t, const float* ac, float gamma,
-                                                            int vpred) {
+                                                            int vpred, const float* q) {
   __shared__ float red[4];
   int gid = blockIdx.x * 256 + threadIdx.x;
   int total = Bn * Lc * HW;
@@ -543,7 +547,16 @@ __global__ __launch_bounds__(256) void mse_loss_grad_kernel(const half_t* pred, 
     float pv = (float)pred[((long long)b * HW + p) * ldp + c];
     float tv = target[((long long)b * Lc + c) * HW + p];
     float d = pv - tv;
-    if constexpr (SNR) {
+    if constexpr (WQ) {
+      float w = q[(long long)b * HW + p];
+      if constexpr (SNR) {
+        float a = ac[t[b]];
+        float snr = a / (1.f - a);
+        w = fminf(snr, gamma) / (vpred ? snr + 1.f : snr) * w;
+      }
+      sq = d * d * w;
+      dpred[((long long)b * HW + p) * lddp + c] = (half_t)(2.f * d * w / (float)total * loss_scale[0]);
+    } else if constexpr (SNR) {
       float a = ac[t[b]];
       float snr = a / (1.f - a);
       float w = fminf(snr, gamma) / (vpred ? snr + 1.f : snr);
@@ -582,6 +595,36 @@ __global__ __launch_bounds__(kMseChunk) void mse_per_sample_kernel(const half_t*
       const float d = (float)pr[c] - tg[(long long)c * HW];
       acc = fmaf(d, d, acc);
     }
+  }
+  red[t] = acc;
+  __syncthreads();
+#pragma unroll
+  for (int s = kMseChunk / 2; s > 0; s >>= 1) {
+    if (t < s) red[t] += red[t + s];
+    __syncthreads();
+  }
+  if (t == 0) ws[(long long)b * nchunk + chunk] = red[0];
+}
+// The weighted sibling: the pixel's channel sum, formed exactly as above, times q[b][p] — one rounded f32
+// product, so q == 1 leaves every partial, and with the shared finish every out[b], bit-identical to the kernel above.
+// The same blocks, the same tree, the same workspace: out[b] = sum_{c,p} q_bp d^2 / (Lc HW).
+__global__ __launch_bounds__(kMseChunk) void mse_per_sample_weighted_kernel(const half_t* __restrict__ pred, long long ldp,
+                                                                            const float* __restrict__ target,
+                                                                            const float* __restrict__ q,
+                                                                            float* __restrict__ ws, int Lc, int HW,
+                                                                            int nchunk) {
+  __shared__ float red[kMseChunk];
+  const int b = blockIdx.y, chunk = blockIdx.x, t = threadIdx.x;
+  const int p = chunk * kMseChunk + t;
+  float acc = 0.f;
+  if (p < HW) {
+    const half_t* pr = pred + ((long long)b * HW + p) * ldp;
+    const float* tg = target + (long long)b * Lc * HW + p;
+    for (int c = 0; c < Lc; ++c) {
+      const float d = (float)pr[c] - tg[(long long)c * HW];
+      acc = fmaf(d, d, acc);
+    }
+    acc *= q[(long long)b * HW + p];
   }
   red[t] = acc;
   __syncthreads();
@@ -1125,7 +1168,7 @@ extern "C" int vneti_mse_loss_grad(const void* pred, long long ldp, const float*
   int n = Bn * Lc * HW;
   hipLaunchKernelGGL(mse_loss_grad_kernel<false>, dim3(cdiv(n, 256)), dim3(256), 0, ST, (const half_t*)pred, ldp, target,
                      (half_t*)dpred, lddp, loss_sum, loss_scale, Bn, Lc, HW, (const long long*)nullptr,
-                     (const float*)nullptr, 0.f, 0);
+                     (const float*)nullptr, 0.f, 0, (const float*)nullptr);
   return vneti_check_launch("mse_loss_grad");
 }
 
@@ -1141,8 +1184,33 @@ extern "C" int vneti_mse_loss_grad_snr(const void* pred, long long ldp, const fl
   int n = Bn * Lc * HW;
   hipLaunchKernelGGL(mse_loss_grad_kernel<true>, dim3(cdiv(n, 256)), dim3(256), 0, ST, (const half_t*)pred, ldp, target,
                      (half_t*)dpred, lddp, loss_sum, loss_scale, Bn, Lc, HW, (const long long*)timesteps,
-                     alphas_cumprod, gamma, v_prediction);
+                     alphas_cumprod, gamma, v_prediction, (const float*)nullptr);
   return vneti_check_launch("mse_loss_grad_snr");
+}
+
+extern "C" int vneti_mse_loss_grad_weighted(const void* pred, long long ldp, const float* target, void* dpred,
+                                            long long lddp, float* loss_sum, const float* loss_scale, const float* q,
+                                            int Bn, int Lc, int HW, const void* timesteps, const float* alphas_cumprod,
+                                            float gamma, int v_prediction, void* stream) {
+  VN_REQUIRE(pred && target && dpred && loss_sum && loss_scale && q, "mse_loss_grad_weighted: null pointer");
+  VN_REQUIRE((timesteps == nullptr) == (alphas_cumprod == nullptr),
+             "mse_loss_grad_weighted: timesteps and alphas_cumprod come as a pair (both null: no Min-SNR factor)");
+  VN_REQUIRE(Bn > 0 && Lc > 0 && HW > 0 && ldp >= Lc && lddp >= Lc && (long long)Bn * Lc * HW < 0x7fffffffLL,
+             "mse_loss_grad_weighted: bad shape Bn=%d Lc=%d HW=%d ldp=%lld lddp=%lld", Bn, Lc, HW, ldp, lddp);
+  VN_REQUIRE((long long)Bn * HW * ldp * 2 < 0x7fffffffLL && (long long)Bn * HW * lddp * 2 < 0x7fffffffLL,
+             "mse_loss_grad_weighted: pred / dpred span 2 GiB or more (Bn=%d HW=%d ldp=%lld lddp=%lld)", Bn, HW, ldp, lddp);
+  int n = Bn * Lc * HW;
+  if (timesteps) {
+    VN_REQUIRE(gamma > 0.f, "mse_loss_grad_weighted: gamma must be > 0 (+inf: every Min-SNR weight is 1)");
+    hipLaunchKernelGGL((mse_loss_grad_kernel<true, true>), dim3(cdiv(n, 256)), dim3(256), 0, ST, (const half_t*)pred, ldp,
+                       target, (half_t*)dpred, lddp, loss_sum, loss_scale, Bn, Lc, HW, (const long long*)timesteps,
+                       alphas_cumprod, gamma, v_prediction, q);
+  } else {
+    hipLaunchKernelGGL((mse_loss_grad_kernel<false, true>), dim3(cdiv(n, 256)), dim3(256), 0, ST, (const half_t*)pred, ldp,
+                       target, (half_t*)dpred, lddp, loss_sum, loss_scale, Bn, Lc, HW, (const long long*)nullptr,
+                       (const float*)nullptr, 0.f, 0, q);
+  }
+  return vneti_check_launch("mse_loss_grad_weighted");
 }
 
 extern "C" long long vneti_mse_loss_per_sample_ws_floats(int Bn, int HW) {
@@ -1160,6 +1228,25 @@ extern "C" int vneti_mse_loss_per_sample(const void* pred, long long ldp, const 
   hipLaunchKernelGGL(mse_per_sample_kernel, dim3(nchunk, Bn), dim3(kMseChunk), 0, ST, (const half_t*)pred, ldp, target, ws,
                      Lc, HW, nchunk);
   const int rc = vneti_check_launch("mse_loss_per_sample");
+  if (rc != VNETI_OK) return rc;
+  hipLaunchKernelGGL(mse_per_sample_finish_kernel, dim3(cdiv(Bn, 256)), dim3(256), 0, ST, (const float*)ws, Bn, nchunk,
+                     1.0 / ((double)Lc * (double)HW), out);
+  return vneti_check_launch("mse_loss_per_sample_finish");
+}
+
+extern "C" int vneti_mse_loss_per_sample_weighted(const void* pred, long long ldp, const float* target, const float* q,
+                                                  float* out, float* ws, int Bn, int Lc, int HW, void* stream) {
+  VN_REQUIRE(pred && target && q && out && ws, "mse_loss_per_sample_weighted: null pointer");
+  VN_REQUIRE(Bn > 0 && Bn <= 65535 && Lc > 0 && HW > 0 && ldp >= Lc,
+             "mse_loss_per_sample_weighted: bad shape Bn=%d Lc=%d HW=%d ldp=%lld (0 < Bn <= 65535, ldp >= Lc)", Bn, Lc, HW,
+             ldp);
+  VN_REQUIRE((long long)Bn * Lc * HW < 0x7fffffffLL, "mse_loss_per_sample_weighted: Bn * Lc * HW over 2^31");
+  VN_REQUIRE((long long)Bn * HW * ldp * 2 < 0x7fffffffLL,
+             "mse_loss_per_sample_weighted: pred spans 2 GiB or more (Bn=%d HW=%d ldp=%lld)", Bn, HW, ldp);
+  const int nchunk = cdiv(HW, kMseChunk);
+  hipLaunchKernelGGL(mse_per_sample_weighted_kernel, dim3(nchunk, Bn), dim3(kMseChunk), 0, ST, (const half_t*)pred, ldp,
+                     target, q, ws, Lc, HW, nchunk);
+  const int rc = vneti_check_launch("mse_loss_per_sample_weighted");
   if (rc != VNETI_OK) return rc;
   hipLaunchKernelGGL(mse_per_sample_finish_kernel, dim3(cdiv(Bn, 256)), dim3(256), 0, ST, (const float*)ws, Bn, nchunk,
                      1.0 / ((double)Lc * (double)HW), out);

@@ -265,6 +265,65 @@ __global__ void to_f32_chw_kernel(const unsigned char* img, float* out, int h, i
   for (int c = 0; c < 3; ++c) out[c * n + gid] = (float)((double)img[gid * 3 + c] / 127.5 - 1.0);
 }
 
+// ---- loss weights from an object mask ---------------------------------------------------------------
+// One latent cell = f x f pixels of a uint8 mask (channel 0 of `ps` interleaved bytes per pixel).  Two launches in a fixed
+// order, integers until the very end: (1) one thread per cell counts its pixels >= thr, leaves the count (exact in f32) in
+// the cell's slot of the output row and the block's integer sum in part[block]; (2) every block adds the partials — an
+// integer sum, so its order cannot matter — and forms, in f64,
+//   m_p = bg + (1 - bg) cnt_p / f^2;  norm = bg hw + (1 - bg) S / f^2;  q_p = m_p (hw / norm), rounded ONCE to f32
+// (norm == 0: the row is exact zeros).  The row is a function of the mask and (H, W, f, thr, bg) alone.
+// VEC8: ps == 1, f == 8 and an 8-byte aligned mask (W % 8 == 0 follows from W % f == 0): a cell's row is one 8-byte load.
+constexpr int kMaskCells = 256;
+template <bool VEC8>
+__global__ __launch_bounds__(kMaskCells) void mask_cell_count_kernel(const unsigned char* __restrict__ mask, int W, int ps,
+                                                                     int f, int thr, int hw, int w, float* __restrict__ q,
+                                                                     int* __restrict__ part) {
+  __shared__ int red[kMaskCells / 64];
+  const int t = threadIdx.x, p = blockIdx.x * kMaskCells + t;
+  int cnt = 0;
+  if (p < hw) {
+    const int cy = p / w, cx = p - cy * w;
+    if constexpr (VEC8) {
+      for (int dy = 0; dy < 8; ++dy) {
+        const uint2 v = *reinterpret_cast<const uint2*>(mask + ((long long)(cy * 8 + dy) * W + cx * 8));
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          cnt += ((int)((v.x >> (8 * k)) & 255u) >= thr) + ((int)((v.y >> (8 * k)) & 255u) >= thr);
+      }
+    } else {
+      for (int dy = 0; dy < f; ++dy) {
+        const unsigned char* row = mask + ((long long)(cy * f + dy) * W + (long long)cx * f) * ps;
+        for (int dx = 0; dx < f; ++dx) cnt += (int)row[(long long)dx * ps] >= thr;
+      }
+    }
+    q[p] = (float)cnt;
+  }
+  int s = cnt;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  if ((t & 63) == 0) red[t >> 6] = s;
+  __syncthreads();
+  if (t == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+__global__ __launch_bounds__(kMaskCells) void mask_weights_finish_kernel(float* __restrict__ q, const int* __restrict__ part,
+                                                                         int nblk, int hw, int f2, float bg_f) {
+  __shared__ long long red[kMaskCells];
+  const int t = threadIdx.x, p = blockIdx.x * kMaskCells + t;
+  long long s = 0;
+  for (int k = t; k < nblk; k += kMaskCells) s += part[k];
+  red[t] = s;
+  __syncthreads();
+  for (int o = kMaskCells / 2; o > 0; o >>= 1) {
+    if (t < o) red[t] += red[t + o];
+    __syncthreads();
+  }
+  if (p >= hw) return;
+  const double bg = (double)bg_f;
+  const double norm = bg * (double)hw + (1.0 - bg) * ((double)red[0] / (double)f2);
+  const double m = bg + (1.0 - bg) * ((double)q[p] / (double)f2);
+  q[p] = norm > 0.0 ? (float)(m * ((double)hw / norm)) : 0.f;
+}
+
 inline unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
@@ -348,6 +407,41 @@ extern "C" int vneti_img_affine_nearest(const void* in, void* out, int h, int w,
                      (unsigned char*)out, h, w, a6_host[0], a6_host[1], a6_host[2], a6_host[3], a6_host[4], a6_host[5],
                      fill);
   return vneti_check_launch("img_affine_nearest");
+}
+
+extern "C" long long vneti_loss_weights_from_mask_ws_ints(int H, int W, int f) {
+  if (H <= 0 || W <= 0 || f <= 0 || f > 64 || H % f || W % f) return -1;
+  const long long hw = (long long)(H / f) * (W / f);
+  if (hw > (1 << 24)) return -1;  // (a cell count is kept as an f32 and a row index as an int)
+  return (hw + kMaskCells - 1) / kMaskCells;
+}
+
+extern "C" int vneti_loss_weights_from_mask(const void* mask, int H, int W, int pixel_stride, int f, int threshold,
+                                            float background, float* q_row, int* ws, void* stream) {
+  VN_REQUIRE(mask && q_row && ws, "loss_weights_from_mask: null pointer");
+  VN_REQUIRE(H > 0 && W > 0 && (pixel_stride == 1 || pixel_stride == 3),
+             "loss_weights_from_mask: bad image H=%d W=%d pixel_stride=%d (stride 1 or 3)", H, W, pixel_stride);
+  VN_REQUIRE(f > 0 && f <= 64 && H % f == 0 && W % f == 0,
+             "loss_weights_from_mask: H=%d W=%d must be multiples of the factor f=%d (0 < f <= 64)", H, W, f);
+  VN_REQUIRE(threshold >= 0 && threshold <= 255, "loss_weights_from_mask: threshold %d outside 0..255", threshold);
+  VN_REQUIRE(background >= 0.f && background <= 1.f, "loss_weights_from_mask: background weight %g outside [0, 1]",
+             (double)background);
+  VN_REQUIRE((long long)H * W * pixel_stride < 0x7fffffffLL, "loss_weights_from_mask: the mask spans 2 GiB or more");
+  const long long nblk = vneti_loss_weights_from_mask_ws_ints(H, W, f);
+  VN_REQUIRE(nblk > 0, "loss_weights_from_mask: %d x %d cells are more than 2^24", H / f, W / f);
+  const int h = H / f, w = W / f, hw = h * w;
+  const unsigned char* m = (const unsigned char*)mask;
+  if (pixel_stride == 1 && f == 8 && ((uintptr_t)m & 7) == 0)
+    hipLaunchKernelGGL(mask_cell_count_kernel<true>, dim3((unsigned)nblk), dim3(kMaskCells), 0, ST, m, W, 1, 8, threshold,
+                       hw, w, q_row, ws);
+  else
+    hipLaunchKernelGGL(mask_cell_count_kernel<false>, dim3((unsigned)nblk), dim3(kMaskCells), 0, ST, m, W, pixel_stride, f,
+                       threshold, hw, w, q_row, ws);
+  const int rc = vneti_check_launch("loss_weights_from_mask");
+  if (rc != VNETI_OK) return rc;
+  hipLaunchKernelGGL(mask_weights_finish_kernel, dim3((unsigned)nblk), dim3(kMaskCells), 0, ST, q_row, (const int*)ws,
+                     (int)nblk, hw, f * f, background);
+  return vneti_check_launch("loss_weights_from_mask_finish");
 }
 
 extern "C" int vneti_img_to_f32_chw(const void* img, float* out, int h, int w, void* stream) {

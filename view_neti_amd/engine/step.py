@@ -56,7 +56,7 @@ class TrainStepEngine:
                  moment_cache_images: int = 0, max_grad_norm: Optional[float] = None, telemetry_rows: int = 0,
                  snr_gamma: Optional[float] = None, noise_offset: Optional[float] = None,
                  ema_decay: Optional[float] = None, ema_update_after_step: int = 0,
-                 ema_warmup_power: Optional[float] = None):
+                 ema_warmup_power: Optional[float] = None, loss_mask: bool = False, loss_mask_background: float = 0.0):
         """mapper_object: one mapper state_dict, or a list of them (learnable_mode 3: one object mapper per
         scene, `mapper_object_lookup`, training/coach.py:505-552) — `set_batch(object_index=k)` picks the one
         the batch trains.
@@ -71,7 +71,12 @@ class TrainStepEngine:
         ema_decay: keep an exponential moving average of the bucket on the device, updated at the end of every applied
         optimizer step (diffusers' EMAModel; None or the cap of the decay, in (0, 1)).  ema_update_after_step delays it,
         ema_warmup_power (None or > 0) picks the 1 - (1 + s)^(-power) ramp over (1 + s) / (10 + s).  The average only reads
-        `params`; ema_weights() swaps it in for evaluation.  Off: no buffer, no launch."""
+        `params`; ema_weights() swaps it in for evaluation.  Off: no buffer, no launch.
+        loss_mask: weight every latent pixel of the training loss by the sample's object mask (`loss_weights`, f32
+        [B][h*w], one row per sample written by set_loss_mask() outside the captured step; ones until then), each sample
+        normalised by its own mask mass.  loss_mask_background in [0, 1]: the weight of a background pixel before the
+        normalisation.  One loss launch swapped for its weighted sibling, none added; eval_losses() stays unmasked.  Off:
+        no buffer, and the step enqueues the launches it always did."""
         from .text import flatten_mapper_state
         # the average's settings (DESIGN §9, f9), refused before anything is built.  (`not a < x < b` also refuses nan)
         if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
@@ -84,6 +89,13 @@ class TrainStepEngine:
             raise ValueError("ema_update_after_step / ema_warmup_power need ema_decay")
         if ema_decay is not None and not need_backward:
             raise ValueError("ema_decay needs an engine that trains")
+        # the object mask's settings
+        if not 0.0 <= float(loss_mask_background) <= 1.0:
+            raise ValueError(f"loss_mask_background must be in [0, 1] (is {loss_mask_background!r})")
+        if not loss_mask and float(loss_mask_background) != 0.0:
+            raise ValueError("loss_mask_background needs loss_mask")
+        if loss_mask and not need_backward:
+            raise ValueError("loss_mask needs an engine that trains")
         self.cfg = cfg
         self.B, self.H, self.W = batch, height, width
         self.dev = device
@@ -205,6 +217,7 @@ class TrainStepEngine:
         self.eval_out = torch.zeros(batch, dtype=torch.float32, device=device)
         self.eval_ws = torch.zeros(ops.mse_loss_per_sample_ws_floats(batch, self.h * self.w), dtype=torch.float32,
                                    device=device)
+        self.eval_out_masked = None  # eval_losses(weights=): allocated on first use
         self.graph_eval = None
         from .staging import HostStager
         self.stager = HostStager()
@@ -275,6 +288,17 @@ class TrainStepEngine:
                                            0.0], dtype=torch.float32, device=device)
             self.ema_coef = torch.zeros(ops.EMA_COEF_FLOATS, dtype=torch.float32, device=device)
             self._STATE = type(self)._STATE + ("ema", "ema_count")  # (this instance's: a state without EMA has neither)
+        # ---- the object-masked objective (settings checked above).  The table is NOT trainer state: it is
+        # rewritten for every batch, like the pixels.  (None where unset: the _WHEN_SET rule)
+        self.loss_mask = True if loss_mask else None
+        self.loss_mask_background = float(loss_mask_background) or None
+        self.loss_weights = self._mask_ws = None
+        self._mask_in = None  # uint8 [B][H][W]: where set_loss_masks() uploads a host batch (allocated on first use)
+        self.vae_factor = 1 << (nlev - 1)
+        if loss_mask:
+            self.loss_weights = torch.ones(batch, self.h * self.w, dtype=torch.float32, device=device)
+            self._mask_ws = torch.zeros(ops.loss_weights_from_mask_ws_ints(height, width, self.vae_factor), dtype=torch.int32,
+                                        device=device)
 
     # ------------------------------------------------------------------ inputs
     def set_batch(self, pixel_values, input_ids, placeholder_object, placeholder_view=None, view_params=None,
@@ -312,6 +336,43 @@ class TrainStepEngine:
                 st.upload("pixels", self.pixel_values, pixel_values)  # (large: a blocking copy, issued LAST)
         finally:
             st.end()
+
+    MASK_THRESHOLD = 3  # process_imgs' binarisation `mask / 255 > 0.01` on uint8: value >= 3
+
+    def set_loss_mask(self, b: int, mask_u8: torch.Tensor, H: int, W: int, pixel_stride: int = 1):
+        """row b of `loss_weights` from sample b's object mask: a uint8 device image [H][W][pixel_stride] (channel 0 is
+        read; stride 3 is what DeviceImagePipeline.run leaves behind) at the engine's training resolution.  Two small
+        launches on the current stream, OUTSIDE the captured step (which only reads the table), like the pixel upload."""
+        if self.loss_weights is None:
+            raise RuntimeError("set_loss_mask(): this engine was built without loss_mask")
+        if not 0 <= b < self.B:
+            raise ValueError(f"set_loss_mask(): sample {b} outside the batch of {self.B}")
+        if (H, W) != (self.H, self.W):
+            raise ValueError(f"set_loss_mask(): a {H}x{W} mask gives a {H // self.vae_factor}x{W // self.vae_factor} latent, "
+                             f"this engine's is {self.h}x{self.w} ({self.H}x{self.W} pixels)")
+        if mask_u8.dtype != torch.uint8 or not mask_u8.is_cuda or mask_u8.numel() < H * W * pixel_stride:
+            raise ValueError("set_loss_mask(): the mask is a uint8 device tensor of H * W * pixel_stride bytes")
+        ops.loss_weights_from_mask(mask_u8, H, W, pixel_stride, self.vae_factor, self.MASK_THRESHOLD,
+                                   self.loss_mask_background or 0.0, self.loss_weights, b, self._mask_ws)
+
+    def set_loss_masks(self, masks_u8: torch.Tensor):
+        """the batch's masks from the host: uint8 [B][H][W], uploaded through the pinned stager, then one set_loss_mask()
+        per sample"""
+        if self.loss_weights is None:
+            raise RuntimeError("set_loss_masks(): this engine was built without loss_mask")
+        if tuple(masks_u8.shape) != (self.B, self.H, self.W) or masks_u8.dtype != torch.uint8:
+            raise ValueError(f"set_loss_masks(): expected uint8 {(self.B, self.H, self.W)}, got {masks_u8.dtype} "
+                             f"{tuple(masks_u8.shape)}")
+        if self._mask_in is None:
+            self._mask_in = torch.zeros(self.B, self.H, self.W, dtype=torch.uint8, device=self.dev)
+        st = self.stager
+        st.begin()
+        try:
+            st.upload("loss_masks", self._mask_in, masks_u8)
+        finally:
+            st.end()
+        for b in range(self.B):
+            self.set_loss_mask(b, self._mask_in[b], self.H, self.W, 1)
 
     def train(self, mode: bool = True):
         """nested dropout is a training-time feature (neti_mapper.py:403); eval() turns the draws off.
@@ -354,7 +415,8 @@ class TrainStepEngine:
     _STATE = ("params", "exp_avg", "exp_avg_sq", "opt_step", "seg_step", "scaler", "rng_state", "hyper")
 
     # described only where set: older states read as "unset"
-    _WHEN_SET = ("max_grad_norm", "snr_gamma", "noise_offset", "ema_decay", "ema_update_after_step", "ema_warmup_power")
+    _WHEN_SET = ("max_grad_norm", "snr_gamma", "noise_offset", "ema_decay", "ema_update_after_step", "ema_warmup_power",
+                 "loss_mask", "loss_mask_background")
 
     def _describe(self) -> Dict:
         from .. import lib
@@ -385,7 +447,7 @@ class TrainStepEngine:
             raise RuntimeError("load_state_dict() inside a gradient-accumulation group")
         want, have = self._describe(), sd.get("meta", {})
         bad = [f"{k}: saved {have.get(k)!r}, this engine {v!r}" for k, v in want.items() if have.get(k) != v]
-        # (a state from before f7 / f8 / f9 has no such keys: unclipped, unweighted, no offset noise, no average)
+        # (a state from before f7 / f8 / f9 / f11 has no such keys: unclipped, unweighted, no offset noise, no average, no mask)
         bad += [f"{k}: saved {have[k]!r}, this engine None" for k in self._WHEN_SET if k in have and k not in want]
         bad += [f"{name}: saved shape {tuple(sd[name].shape) if name in sd else None}, this engine "
                 f"{tuple(getattr(self, name).shape)}" for name in self._STATE
@@ -414,13 +476,22 @@ class TrainStepEngine:
             raise RuntimeError("noise_offset without the device RNG: set_noise(..., offset_noise=) has to deliver the draw")
         self._forward_half(cached, bool(self.n_cache), fork=self.overlap, noise_offset=self.noise_offset)
         self.loss_sum.zero_()
-        if self.snr_gamma is None:
+        vpred = self.cfg.ddpm.prediction_type == "v_prediction"
+        if self.loss_weights is not None:  # (the same single launch, with the mask's weights and the null-able SNR pair)
+            snr = {} if self.snr_gamma is None else dict(t=self.timesteps, ac=self.ac, gamma=self.snr_gamma, vpred=vpred)
+            ops.mse_loss_grad_weighted(self.unet.pred, self.target, self.unet.dpred, self.loss_sum, self.scaler,
+                                       self.loss_weights, B, Lc, hw, **snr)
+        elif self.snr_gamma is None:
             ops.mse_loss_grad(self.unet.pred, self.target, self.unet.dpred, self.loss_sum, self.scaler, B, Lc, hw)
         else:
             ops.mse_loss_grad_snr(self.unet.pred, self.target, self.unet.dpred, self.loss_sum, self.scaler, B, Lc, hw,
-                                  self.timesteps, self.ac, self.snr_gamma, self.cfg.ddpm.prediction_type == "v_prediction")
+                                  self.timesteps, self.ac, self.snr_gamma, vpred)
         if self.telemetry_rows:  # the micro-step's row: timesteps + the deterministic per-sample losses, then count += 1
-            ops.mse_loss_per_sample(self.unet.pred, self.target, self.rec_loss, self.rec_ws, B, Lc, hw)
+            if self.loss_weights is not None:  # (the masked ones: what the step minimises, before the Min-SNR weight)
+                ops.mse_loss_per_sample_weighted(self.unet.pred, self.target, self.loss_weights, self.rec_loss, self.rec_ws,
+                                                 B, Lc, hw)
+            else:
+                ops.mse_loss_per_sample(self.unet.pred, self.target, self.rec_loss, self.rec_ws, B, Lc, hw)
             ops.train_record(self.tele_ring, self.tele_count, self.telemetry_rows, not accumulate, self.timesteps,
                              self.rec_loss, B)
         if self.need_backward:
@@ -574,20 +645,33 @@ class TrainStepEngine:
         finally:
             self.text.training = mode
 
-    def eval_losses(self, graph: bool = True) -> torch.Tensor:
+    def eval_losses(self, graph: bool = True, weights: Optional[torch.Tensor] = None):
         """per-sample diffusion losses of the current batch, CPU float32 [B] (forces a device sync).  Legal between
         optimizer steps only.  graph=True replays `graph_eval`, captured on first use (and again by capture());
-        graph=False launches eagerly."""
+        graph=False launches eagerly.  They are unmasked whatever the engine was built with.
+        weights: f32 device [B][h*w] (rows of vneti_loss_weights_from_mask, e.g. `loss_weights`): returns the pair
+        (unmasked, masked); the masked ones are one more per-sample launch behind the same forward."""
         if self.micro != 0:
             raise ValueError(f"eval_losses() inside a gradient-accumulation group (micro-step {self.micro} of "
                              f"{self.grad_accum}): legal between optimizer steps only")
+        if weights is not None:
+            if tuple(weights.shape) != (self.B, self.h * self.w) or weights.dtype != torch.float32 or not weights.is_cuda \
+                    or not weights.is_contiguous():
+                raise ValueError(f"eval_losses(): weights must be a contiguous f32 device tensor {(self.B, self.h * self.w)}")
+            if self.eval_out_masked is None:
+                self.eval_out_masked = torch.zeros_like(self.eval_out)
         if not graph:
             self.eval_forward()
         else:
             if self.graph_eval is None:
                 self._capture_eval()
             self.graph_eval.replay()
-        return self.eval_out.cpu()
+        if weights is None:
+            return self.eval_out.cpu()
+        # (outside the captured evaluation: the graph, its launches and its numbers do not know about the mask)
+        B, Lc, hw = self.B, self.cfg.vae.latent_channels, self.h * self.w
+        ops.mse_loss_per_sample_weighted(self.unet.pred, self.target, weights, self.eval_out_masked, self.eval_ws, B, Lc, hw)
+        return self.eval_out.cpu(), self.eval_out_masked.cpu()
 
     def _capture_eval(self):
         """the warm-up launch is an evaluation itself: nothing to snapshot"""
@@ -775,4 +859,5 @@ class TrainStepEngine:
         return out
 
     def memory_bytes(self) -> int:
-        return self.unet.bytes + self.vae.bytes + self.text.bytes
+        own = 0 if self.loss_weights is None else self.loss_weights.numel() * 4 + self._mask_ws.numel() * 4
+        return self.unet.bytes + self.vae.bytes + self.text.bytes + own

@@ -127,7 +127,8 @@ SIGNATURES = {n[len("vneti_"):]: argtypes for n, (_, argtypes) in _PROTOS.items(
 VALUE_FUNCS = frozenset({
     "version", "precision", "last_error", "gemm_select_tile", "gemm_select_split", "attn_dkv_qsplit", "img_resample_ksize",
     "groupnorm_ws_floats", "lpips_ws_floats", "mse_loss_per_sample_ws_floats", "mapper_num_params", "mapper_save_floats",
-    "mapper_rowgrad_floats", "mapper_legacy_input_params", "grad_sumsq_ws_doubles", "cfg_rescale_ws_doubles"})
+    "mapper_rowgrad_floats", "mapper_legacy_input_params", "grad_sumsq_ws_doubles", "cfg_rescale_ws_doubles",
+    "loss_weights_from_mask_ws_ints"})
 _stray = ({n[len("vneti_"):] for n, (res, _) in _PROTOS.items() if res is C.c_longlong} - VALUE_FUNCS) | (VALUE_FUNCS - set(SIGNATURES))
 if _stray:
     raise RuntimeError(f"lib.VALUE_FUNCS is out of step with include/vneti.h: {sorted(_stray)}")

@@ -388,6 +388,44 @@ def mse_loss_per_sample(pred, target, out, ws, Bn, Lc, HW):
     _l.call("mse_loss_per_sample", _p(pred), _ld(pred), _p(target), _p(out), _p(ws), Bn, Lc, HW, stream())
 
 
+def loss_weights_from_mask_ws_ints(H, W, f):
+    n = _l.query("loss_weights_from_mask_ws_ints", H, W, f)
+    if n < 0:
+        raise RuntimeError(f"loss_weights_from_mask: unsupported shape H={H} W={W} f={f} (H and W multiples of f, f <= 64)")
+    return n
+
+
+def loss_weights_from_mask(mask, H, W, pixel_stride, f, threshold, background, q, b, ws):
+    """row b of q (f32 [Bn][h*w]) from one uint8 mask image [H][W][pixel_stride] (channel 0): the normalised per-cell loss
+    weights of include/vneti.h; ws: int32 scratch of loss_weights_from_mask_ws_ints(H, W, f)"""
+    assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() >= H * W * pixel_stride
+    assert q.dtype == torch.float32 and q.dim() == 2 and q.stride(1) == 1 and 0 <= b < q.shape[0]
+    assert ws.dtype == torch.int32
+    if q.shape[1] != (H // f) * (W // f) or ws.numel() < loss_weights_from_mask_ws_ints(H, W, f):
+        raise ValueError(f"loss_weights_from_mask: a {H}x{W} mask at factor {f} does not fill rows of {q.shape[1]} weights")
+    _l.call("loss_weights_from_mask", _p(mask), H, W, pixel_stride, f, int(threshold), float(background), _p(q[b]), _p(ws),
+            stream())
+
+
+def mse_loss_grad_weighted(pred, target, dpred, loss_sum, loss_scale, q, Bn, Lc, HW, t=None, ac=None, gamma=0.0,
+                           vpred=False):
+    """mse_loss_grad (t and ac None) or mse_loss_grad_snr with every term weighted by q[b][p] as well (f32 [Bn][HW])"""
+    assert q.dtype == torch.float32 and q.is_contiguous() and q.numel() >= Bn * HW
+    assert (t is None) == (ac is None)
+    if t is not None:
+        assert t.dtype == torch.int64 and t.numel() >= Bn and ac.dtype == torch.float32
+    _l.call("mse_loss_grad_weighted", _p(pred), _ld(pred), _p(target), _p(dpred), _ld(dpred), _p(loss_sum), _p(loss_scale),
+            _p(q), Bn, Lc, HW, _p(t), _p(ac), float(gamma), 1 if vpred else 0, stream())
+
+
+def mse_loss_per_sample_weighted(pred, target, q, out, ws, Bn, Lc, HW):
+    """out[b] = sum over (c, p) of q[b][p] (pred - target)^2 / (Lc HW) (mse_loss_per_sample with the weights of the step)"""
+    assert out.dtype == torch.float32 and out.numel() >= Bn and ws.dtype == torch.float32
+    assert q.dtype == torch.float32 and q.is_contiguous() and q.numel() >= Bn * HW
+    assert ws.numel() >= mse_loss_per_sample_ws_floats(Bn, HW), "mse_loss_per_sample_weighted: workspace too small"
+    _l.call("mse_loss_per_sample_weighted", _p(pred), _ld(pred), _p(target), _p(q), _p(out), _p(ws), Bn, Lc, HW, stream())
+
+
 OPT_CHECK, OPT_APPLY, OPT_FINISH, OPT_ALL = 1, 2, 4, 7
 
 
