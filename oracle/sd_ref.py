@@ -31,6 +31,15 @@ import torch.nn.functional as F
 W = Dict[str, torch.Tensor]
 
 
+def _tap(taps, key, t):
+    """Named taps: the graph functions below take an optional dict `taps` and record intermediate tensors in it (detached,
+    in call order, under the parameter prefix of the layer that made them) so that the engine tests can compare the buffers
+    inside an engine and not only its end result.  With taps=None nothing is recorded and nothing else changes."""
+    if taps is not None:
+        assert key not in taps, key
+        taps[key] = t.detach()
+
+
 # ------------------------------------------------------------------------------------------
 # reference-owned: positional encoding + NeTI mapper (arch_view_net = 15)
 # ------------------------------------------------------------------------------------------
@@ -143,8 +152,10 @@ def _act(x, kind):
     return F.gelu(x)
 
 
-def clip_encoder(w: W, cfg, x: torch.Tensor) -> torch.Tensor:
-    """x: (B, L, D) embeddings -> last hidden state BEFORE final_layer_norm."""
+def clip_encoder(w: W, cfg, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
+    """x: (B, L, D) embeddings -> last hidden state BEFORE final_layer_norm.
+    taps, per layer prefix: ln1, ln2 (the LayerNorm outputs), qkv (the three projections side by side), attn (the residual
+    stream after self-attention + out_proj), mlp (the residual stream after the MLP)."""
     B, L, D = x.shape
     H = cfg.num_heads
     hd = D // H
@@ -153,19 +164,26 @@ def clip_encoder(w: W, cfg, x: torch.Tensor) -> torch.Tensor:
         p = f"text_model.encoder.layers.{i}."
         r = x
         h = F.layer_norm(x, (D,), w[p + "layer_norm1.weight"], w[p + "layer_norm1.bias"], cfg.eps)
+        _tap(taps, p + "ln1", h)
         q = F.linear(h, w[p + "self_attn.q_proj.weight"], w[p + "self_attn.q_proj.bias"]) * hd ** -0.5
         k = F.linear(h, w[p + "self_attn.k_proj.weight"], w[p + "self_attn.k_proj.bias"])
         v = F.linear(h, w[p + "self_attn.v_proj.weight"], w[p + "self_attn.v_proj.bias"])
+        if taps is not None:  # (q before its scaling)
+            _tap(taps, p + "qkv", torch.cat([F.linear(h, w[p + "self_attn.q_proj.weight"], w[p + "self_attn.q_proj.bias"]),
+                                             k, v], -1))
         q = q.view(B, L, H, hd).transpose(1, 2)
         k = k.view(B, L, H, hd).transpose(1, 2)
         v = v.view(B, L, H, hd).transpose(1, 2)
         a = torch.softmax(q @ k.transpose(-1, -2) + mask, -1)
         o = (a @ v).transpose(1, 2).reshape(B, L, D)
         x = r + F.linear(o, w[p + "self_attn.out_proj.weight"], w[p + "self_attn.out_proj.bias"])
+        _tap(taps, p + "attn", x)
         r = x
         h = F.layer_norm(x, (D,), w[p + "layer_norm2.weight"], w[p + "layer_norm2.bias"], cfg.eps)
+        _tap(taps, p + "ln2", h)
         h = _act(F.linear(h, w[p + "mlp.fc1.weight"], w[p + "mlp.fc1.bias"]), cfg.act)
         x = r + F.linear(h, w[p + "mlp.fc2.weight"], w[p + "mlp.fc2.bias"])
+        _tap(taps, p + "mlp", x)
     return x
 
 
@@ -214,13 +232,13 @@ def apply_bypass(last_hidden: torch.Tensor, input_ids: torch.Tensor, placeholder
 
 def neti_text_encoder(w: W, cfg, input_ids, placeholder_object, word_object, bypass_object,
                       unconstrained_object=False, alpha_object=0.2, placeholder_view=None, word_view=None,
-                      bypass_view=None, unconstrained_view=False, alpha_view=0.2):
+                      bypass_view=None, unconstrained_view=False, alpha_view=0.2, taps: Optional[dict] = None):
     """NeTICLIPTextTransformer.forward (models/neti_clip_text_encoder.py:57-225), `batch=` branch.
     Returns (last_hidden_state, last_hidden_state_with_bypass | None), both after final LN."""
     x = neti_embeddings(w["text_model.embeddings.token_embedding.weight"],
                         w["text_model.embeddings.position_embedding.weight"], input_ids,
                         placeholder_object, word_object, placeholder_view, word_view)
-    last = clip_encoder(w, cfg, x)
+    last = clip_encoder(w, cfg, x, taps)
     lnw, lnb = w["text_model.final_layer_norm.weight"], w["text_model.final_layer_norm.bias"]
     D = last.shape[-1]
     with_bypass = None
@@ -287,36 +305,51 @@ def timestep_embedding(t: torch.Tensor, dim: int) -> torch.Tensor:
     return torch.cat([torch.cos(e), torch.sin(e)], dim=-1)  # flip_sin_to_cos=True
 
 
-def _resnet(w: W, p: str, x, temb, groups, eps):
+def _resnet(w: W, p: str, x, temb, groups, eps, taps: Optional[dict] = None):
+    """taps under p: gn1, gn2 (the two GroupNorm-SiLU outputs), h1 (conv1 + time-embedding add), out"""
     h = F.silu(F.group_norm(x, groups, w[p + "norm1.weight"], w[p + "norm1.bias"], eps))
+    _tap(taps, p + "gn1", h)
     h = F.conv2d(h, w[p + "conv1.weight"], w[p + "conv1.bias"], padding=1)
     if temb is not None:
         h = h + F.linear(F.silu(temb), w[p + "time_emb_proj.weight"], w[p + "time_emb_proj.bias"])[:, :, None, None]
+    _tap(taps, p + "h1", h)
     h = F.silu(F.group_norm(h, groups, w[p + "norm2.weight"], w[p + "norm2.bias"], eps))
+    _tap(taps, p + "gn2", h)
     h = F.conv2d(h, w[p + "conv2.weight"], w[p + "conv2.bias"], padding=1)
     if (p + "conv_shortcut.weight") in w:
         x = F.conv2d(x, w[p + "conv_shortcut.weight"], w[p + "conv_shortcut.bias"])
-    return x + h
+    out = x + h
+    _tap(taps, p + "out", out)
+    return out
 
 
-def _transformer(w: W, p: str, x, ctx, heads, groups, linear_proj):
+def _transformer(w: W, p: str, x, ctx, heads, groups, linear_proj, taps: Optional[dict] = None):
+    """taps under p: gn (the GroupNorm output), h0 (proj_in), ln1..ln3 (the three LayerNorm outputs), h1, h2 (after attn1
+    and attn2), out; h0..h2 and ln1..ln3 are (B, H*W, C)"""
     B, C, H, Wd = x.shape
     res = x
     h = F.group_norm(x, groups, w[p + "norm.weight"], w[p + "norm.bias"], 1e-6)
+    _tap(taps, p + "gn", h)
     if linear_proj:
         h = h.permute(0, 2, 3, 1).reshape(B, H * Wd, C)
         h = F.linear(h, w[p + "proj_in.weight"], w[p + "proj_in.bias"])
     else:
         h = F.conv2d(h, w[p + "proj_in.weight"], w[p + "proj_in.bias"])
         h = h.permute(0, 2, 3, 1).reshape(B, H * Wd, C)
+    _tap(taps, p + "h0", h)
     t = p + "transformer_blocks.0."
     n = F.layer_norm(h, (C,), w[t + "norm1.weight"], w[t + "norm1.bias"])
+    _tap(taps, p + "ln1", n)
     h = h + xti_attention(w[t + "attn1.to_q.weight"], w[t + "attn1.to_k.weight"], w[t + "attn1.to_v.weight"],
                           w[t + "attn1.to_out.0.weight"], w[t + "attn1.to_out.0.bias"], heads, n, None)
+    _tap(taps, p + "h1", h)
     n = F.layer_norm(h, (C,), w[t + "norm2.weight"], w[t + "norm2.bias"])
+    _tap(taps, p + "ln2", n)
     h = h + xti_attention(w[t + "attn2.to_q.weight"], w[t + "attn2.to_k.weight"], w[t + "attn2.to_v.weight"],
                           w[t + "attn2.to_out.0.weight"], w[t + "attn2.to_out.0.bias"], heads, n, ctx)
+    _tap(taps, p + "h2", h)
     n = F.layer_norm(h, (C,), w[t + "norm3.weight"], w[t + "norm3.bias"])
+    _tap(taps, p + "ln3", n)
     g = F.linear(n, w[t + "ff.net.0.proj.weight"], w[t + "ff.net.0.proj.bias"])
     a, gate = g.chunk(2, dim=-1)
     h = h + F.linear(a * F.gelu(gate), w[t + "ff.net.2.weight"], w[t + "ff.net.2.bias"])
@@ -326,77 +359,100 @@ def _transformer(w: W, p: str, x, ctx, heads, groups, linear_proj):
     else:
         h = h.reshape(B, H, Wd, C).permute(0, 3, 1, 2)
         h = F.conv2d(h, w[p + "proj_out.weight"], w[p + "proj_out.bias"])
-    return h + res
+    out = h + res
+    _tap(taps, p + "out", out)
+    return out
 
 
-def unet_forward(w: W, cfg, sample: torch.Tensor, timesteps: torch.Tensor, ctx) -> torch.Tensor:
-    """sample (B,4,h,w), timesteps (B,), ctx = XTI dict or tensor -> predicted noise (B,4,h,w)."""
+def unet_forward(w: W, cfg, sample: torch.Tensor, timesteps: torch.Tensor, ctx,
+                 taps: Optional[dict] = None) -> torch.Tensor:
+    """sample (B,4,h,w), timesteps (B,), ctx = XTI dict or tensor -> predicted noise (B,4,h,w).
+    taps (besides those of _resnet / _transformer): time.sin, time.h = SiLU(linear_1), time.emb = SiLU(linear_2) — the
+    SiLU that every consumer of the embedding applies first —, conv_in, every <down/upsampler prefix>out, conv_norm_out.y"""
     G, eps = cfg.norm_num_groups, cfg.norm_eps
     boc = cfg.block_out_channels
     temb = timestep_embedding(timesteps, boc[0])
+    _tap(taps, "time.sin", temb)
     temb = F.linear(temb, w["time_embedding.linear_1.weight"], w["time_embedding.linear_1.bias"])
+    if taps is not None:
+        _tap(taps, "time.h", F.silu(temb))
     temb = F.linear(F.silu(temb), w["time_embedding.linear_2.weight"], w["time_embedding.linear_2.bias"])
+    if taps is not None:
+        _tap(taps, "time.emb", F.silu(temb))
     h = F.conv2d(sample, w["conv_in.weight"], w["conv_in.bias"], padding=1)
+    _tap(taps, "conv_in", h)
     skips = [h]
     for i in range(len(boc)):
         for j in range(cfg.layers_per_block):
-            h = _resnet(w, f"down_blocks.{i}.resnets.{j}.", h, temb, G, eps)
+            h = _resnet(w, f"down_blocks.{i}.resnets.{j}.", h, temb, G, eps, taps)
             if cfg.down_has_attn[i]:
                 h = _transformer(w, f"down_blocks.{i}.attentions.{j}.", h, ctx, cfg.num_heads[i], G,
-                                 cfg.use_linear_projection)
+                                 cfg.use_linear_projection, taps)
             skips.append(h)
         if i < len(boc) - 1:
             p = f"down_blocks.{i}.downsamplers.0.conv."
             h = F.conv2d(h, w[p + "weight"], w[p + "bias"], stride=2, padding=1)
+            _tap(taps, p + "out", h)
             skips.append(h)
-    h = _resnet(w, "mid_block.resnets.0.", h, temb, G, eps)
-    h = _transformer(w, "mid_block.attentions.0.", h, ctx, cfg.num_heads[-1], G, cfg.use_linear_projection)
-    h = _resnet(w, "mid_block.resnets.1.", h, temb, G, eps)
+    h = _resnet(w, "mid_block.resnets.0.", h, temb, G, eps, taps)
+    h = _transformer(w, "mid_block.attentions.0.", h, ctx, cfg.num_heads[-1], G, cfg.use_linear_projection, taps)
+    h = _resnet(w, "mid_block.resnets.1.", h, temb, G, eps, taps)
     up_has_attn = tuple(reversed(cfg.down_has_attn))
     up_heads = tuple(reversed(cfg.num_heads))
     for i in range(len(boc)):
         for j in range(cfg.layers_per_block + 1):
             h = torch.cat([h, skips.pop()], dim=1)
-            h = _resnet(w, f"up_blocks.{i}.resnets.{j}.", h, temb, G, eps)
+            h = _resnet(w, f"up_blocks.{i}.resnets.{j}.", h, temb, G, eps, taps)
             if up_has_attn[i]:
                 h = _transformer(w, f"up_blocks.{i}.attentions.{j}.", h, ctx, up_heads[i], G,
-                                 cfg.use_linear_projection)
+                                 cfg.use_linear_projection, taps)
         if i < len(boc) - 1:
             p = f"up_blocks.{i}.upsamplers.0.conv."
             h = F.interpolate(h, scale_factor=2.0, mode="nearest")
             h = F.conv2d(h, w[p + "weight"], w[p + "bias"], padding=1)
+            _tap(taps, p + "out", h)
     h = F.silu(F.group_norm(h, G, w["conv_norm_out.weight"], w["conv_norm_out.bias"], eps))
+    _tap(taps, "conv_norm_out.y", h)
     return F.conv2d(h, w["conv_out.weight"], w["conv_out.bias"], padding=1)
 
 
 # ------------------------------------------------------------------------------------------
 # third-party: AutoencoderKL.encode (diffusers 0.14), SURVEY App. A.3 — PARITY UNPINNED
 # ------------------------------------------------------------------------------------------
-def vae_encode_moments(w: W, cfg, x: torch.Tensor) -> torch.Tensor:
-    """x (B,3,H,W) in [-1,1] -> moments (B, 2*latent, H/8, W/8) = quant_conv(encoder(x))."""
+def vae_encode_moments(w: W, cfg, x: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
+    """x (B,3,H,W) in [-1,1] -> moments (B, 2*latent, H/8, W/8) = quant_conv(encoder(x)).
+    taps (besides those of _resnet): encoder.conv_in, every downsampler's out, the mid attention's gn (GroupNorm output),
+    qkv (the three projections side by side) and out (with the residual), encoder.conv_norm_out.y"""
     G, eps = cfg.norm_num_groups, cfg.norm_eps
     boc = cfg.block_out_channels
     h = F.conv2d(x, w["encoder.conv_in.weight"], w["encoder.conv_in.bias"], padding=1)
+    _tap(taps, "encoder.conv_in", h)
     for i in range(len(boc)):
         for j in range(cfg.layers_per_block):
-            h = _resnet(w, f"encoder.down_blocks.{i}.resnets.{j}.", h, None, G, eps)
+            h = _resnet(w, f"encoder.down_blocks.{i}.resnets.{j}.", h, None, G, eps, taps)
         if i < len(boc) - 1:
             p = f"encoder.down_blocks.{i}.downsamplers.0.conv."
             h = F.conv2d(F.pad(h, (0, 1, 0, 1)), w[p + "weight"], w[p + "bias"], stride=2)
-    h = _resnet(w, "encoder.mid_block.resnets.0.", h, None, G, eps)
+            _tap(taps, p + "out", h)
+    h = _resnet(w, "encoder.mid_block.resnets.0.", h, None, G, eps, taps)
     a = "encoder.mid_block.attentions.0."
     B, C, H, Wd = h.shape
     res = h
     n = F.group_norm(h, G, w[a + "group_norm.weight"], w[a + "group_norm.bias"], eps)
+    _tap(taps, a + "gn", n)
     n = n.view(B, C, H * Wd).transpose(1, 2)
     q = F.linear(n, w[a + "query.weight"], w[a + "query.bias"])
     k = F.linear(n, w[a + "key.weight"], w[a + "key.bias"])
     v = F.linear(n, w[a + "value.weight"], w[a + "value.bias"])
+    if taps is not None:
+        _tap(taps, a + "qkv", torch.cat([q, k, v], -1))
     probs = torch.softmax(q @ k.transpose(-1, -2) / math.sqrt(C), -1)
     o = F.linear(probs @ v, w[a + "proj_attn.weight"], w[a + "proj_attn.bias"])
     h = o.transpose(1, 2).reshape(B, C, H, Wd) + res
-    h = _resnet(w, "encoder.mid_block.resnets.1.", h, None, G, eps)
+    _tap(taps, a + "out", h)
+    h = _resnet(w, "encoder.mid_block.resnets.1.", h, None, G, eps, taps)
     h = F.silu(F.group_norm(h, G, w["encoder.conv_norm_out.weight"], w["encoder.conv_norm_out.bias"], eps))
+    _tap(taps, "encoder.conv_norm_out.y", h)
     h = F.conv2d(h, w["encoder.conv_out.weight"], w["encoder.conv_out.bias"], padding=1)
     return F.conv2d(h, w["quant_conv.weight"], w["quant_conv.bias"])
 
@@ -434,9 +490,10 @@ def get_velocity(ac: torch.Tensor, x0, noise, t):
 # ------------------------------------------------------------------------------------------
 def text_conditioning(clip_w: W, clip_cfg, mapper_p: W, w_enc, norm_scale, input_ids, placeholder_object,
                       timesteps, alpha=0.2, unconstrained=False, n_layers=16, view=None, hidden_masks=None,
-                      output_bypass=True):
+                      output_bypass=True, taps: Optional[list] = None):
     """Coach.get_text_conditioning (training/coach.py:276-311): one text-encoder pass per UNet
     cross-attention layer; returns the XTI context dict.
+    taps: optional LIST; pass l appends the dict of its clip_encoder taps.
     view = optional dict(p, w_enc, norm_scale, placeholder, params, alpha, unconstrained, hidden_masks).
     hidden_masks: optional [n_layers, B, hidden] 0/1 nested-dropout masks (neti_mapper.py:401-414)."""
     hs = {"this_idx": 0}
@@ -458,6 +515,9 @@ def text_conditioning(clip_w: W, clip_cfg, mapper_p: W, w_enc, norm_scale, input
                                     truncation_mask=None if vm is None else vm[l])
             kw = dict(placeholder_view=view["placeholder"], word_view=wv, bypass_view=bv,
                       unconstrained_view=view.get("unconstrained", False), alpha_view=view.get("alpha", alpha))
+        if taps is not None:
+            taps.append({})
+            kw["taps"] = taps[-1]
         last, last_b = neti_text_encoder(clip_w, clip_cfg, input_ids, placeholder_object, word, byp,
                                          unconstrained, alpha, **kw)
         hs[f"CONTEXT_TENSOR_{l}"] = last
@@ -468,22 +528,26 @@ def text_conditioning(clip_w: W, clip_cfg, mapper_p: W, w_enc, norm_scale, input
 
 def train_step_loss(sd_cfg, unet_w, vae_w, clip_w, mapper_p, w_enc, norm_scale, pixel_values, input_ids,
                     placeholder_object, timesteps, eps_latent, noise, alpha=0.2, unconstrained=False,
-                    ctx_round=None, view=None):
-    """Forward of one micro-step; returns (loss, aux).  `ctx_round` optionally rounds the context
+                    ctx_round=None, view=None, taps: Optional[dict] = None):
+    """Forward of one micro-step; returns (loss, aux).  taps: optional dict, filled with "vae" and "unet" (the dicts of
+    vae_encode_moments / unet_forward) and "text" (the list of text_conditioning).  `ctx_round` optionally rounds the context
     tensors (e.g. lambda t: t.half().float()) to mimic the reference's `.to(weight_dtype)`
     (training/coach.py:299-304)."""
     with torch.no_grad():
-        moments = vae_encode_moments(vae_w, sd_cfg.vae, pixel_values)
+        if taps is not None:
+            taps.update(vae={}, text=[], unet={})
+        moments = vae_encode_moments(vae_w, sd_cfg.vae, pixel_values, None if taps is None else taps["vae"])
         latents = gaussian_sample(moments, eps_latent) * sd_cfg.vae.scaling_factor
         ac = alphas_cumprod(sd_cfg.ddpm)
         noisy = add_noise(ac, latents, noise, timesteps)
     hs = text_conditioning(clip_w, sd_cfg.clip, mapper_p, w_enc, norm_scale, input_ids, placeholder_object,
-                           timesteps, alpha, unconstrained, sd_cfg.unet.n_cross_layers, view=view)
+                           timesteps, alpha, unconstrained, sd_cfg.unet.n_cross_layers, view=view,
+                           taps=None if taps is None else taps["text"])
     if ctx_round is not None:
         for k in list(hs):
             if k != "this_idx" and hs[k] is not None:
                 hs[k] = ctx_round(hs[k])
-    pred = unet_forward(unet_w, sd_cfg.unet, noisy, timesteps, hs)
+    pred = unet_forward(unet_w, sd_cfg.unet, noisy, timesteps, hs, None if taps is None else taps["unet"])
     if sd_cfg.ddpm.prediction_type == "epsilon":
         target = noise
     else:
@@ -505,32 +569,42 @@ def adamw_step(p, g, m, v, step, lr, b1=0.9, b2=0.999, eps=1e-8, wd=1e-2):
 # inference path: AutoencoderKL.decode, DPM-Solver++(2M) / DDIM, sd_pipeline_call
 # third-party pieces follow diffusers 0.14 — PARITY UNPINNED (diffusers is not installable here)
 # ------------------------------------------------------------------------------------------
-def vae_decode(w: W, cfg, z: torch.Tensor) -> torch.Tensor:
+def vae_decode(w: W, cfg, z: torch.Tensor, taps: Optional[dict] = None) -> torch.Tensor:
     """z (B,latent,h,w) already divided by the scaling factor -> image (B,3,8h,8w) in ~[-1,1]
-    (`pipeline.decode_latents`, sd_pipeline_call.py:115: post_quant_conv -> Decoder)."""
+    (`pipeline.decode_latents`, sd_pipeline_call.py:115: post_quant_conv -> Decoder).
+    taps (besides those of _resnet): post_quant_conv, decoder.conv_in, the mid attention's gn, qkv and out, every upsampler's
+    out, decoder.conv_norm_out.y"""
     G, eps = cfg.norm_num_groups, cfg.norm_eps
     boc = list(reversed(cfg.block_out_channels))
     h = F.conv2d(z, w["post_quant_conv.weight"], w["post_quant_conv.bias"])
+    _tap(taps, "post_quant_conv", h)
     h = F.conv2d(h, w["decoder.conv_in.weight"], w["decoder.conv_in.bias"], padding=1)
-    h = _resnet(w, "decoder.mid_block.resnets.0.", h, None, G, eps)
+    _tap(taps, "decoder.conv_in", h)
+    h = _resnet(w, "decoder.mid_block.resnets.0.", h, None, G, eps, taps)
     a = "decoder.mid_block.attentions.0."
     B, C, H, Wd = h.shape
     n = F.group_norm(h, G, w[a + "group_norm.weight"], w[a + "group_norm.bias"], eps)
+    _tap(taps, a + "gn", n)
     n = n.view(B, C, H * Wd).transpose(1, 2)
     q = F.linear(n, w[a + "query.weight"], w[a + "query.bias"])
     k = F.linear(n, w[a + "key.weight"], w[a + "key.bias"])
     v = F.linear(n, w[a + "value.weight"], w[a + "value.bias"])
+    if taps is not None:
+        _tap(taps, a + "qkv", torch.cat([q, k, v], -1))
     probs = torch.softmax(q @ k.transpose(-1, -2) / math.sqrt(C), -1)
     o = F.linear(probs @ v, w[a + "proj_attn.weight"], w[a + "proj_attn.bias"])
     h = o.transpose(1, 2).reshape(B, C, H, Wd) + h
-    h = _resnet(w, "decoder.mid_block.resnets.1.", h, None, G, eps)
+    _tap(taps, a + "out", h)
+    h = _resnet(w, "decoder.mid_block.resnets.1.", h, None, G, eps, taps)
     for i in range(len(boc)):
         for j in range(cfg.layers_per_block + 1):
-            h = _resnet(w, f"decoder.up_blocks.{i}.resnets.{j}.", h, None, G, eps)
+            h = _resnet(w, f"decoder.up_blocks.{i}.resnets.{j}.", h, None, G, eps, taps)
         if i < len(boc) - 1:
             p = f"decoder.up_blocks.{i}.upsamplers.0.conv."
             h = F.conv2d(F.interpolate(h, scale_factor=2.0, mode="nearest"), w[p + "weight"], w[p + "bias"], padding=1)
+            _tap(taps, p + "out", h)
     h = F.silu(F.group_norm(h, G, w["decoder.conv_norm_out.weight"], w["decoder.conv_norm_out.bias"], eps))
+    _tap(taps, "decoder.conv_norm_out.y", h)
     return F.conv2d(h, w["decoder.conv_out.weight"], w["decoder.conv_out.bias"], padding=1)
 
 

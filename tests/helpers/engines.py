@@ -63,13 +63,19 @@ def mapper_args(cfg_name, n_obj=1, with_view=False, perturb_seed=1, fork_rng=Fal
     return (states[0] if n_obj == 1 else states[:n_obj]), w_enc, view
 
 
-def build_train_engine(cfg_name, B, H, W, n_obj=1, with_view=False, perturb_seed=1, fork_rng=False, order=W_ENC_FIRST, **kw):
+def build_train_engine(cfg_name, B, H, W, n_obj=1, with_view=False, perturb_seed=1, fork_rng=False, order=W_ENC_FIRST,
+                       loud_seed=None, **kw):
     """-> cfg, eng, (uw, vw, cw), object state(s), w_enc, view keyword arguments.  The synthetic weights of the tiny families
-    stay on the host (the engine packs them), the full-size ones are made on the device; **kw goes to the engine."""
+    stay on the host (the engine packs them), the full-size ones are made on the device; **kw goes to the engine.
+    loud_seed: the 1-D tensors of the three frozen models are replaced by helpers/loud_weights.py's (seeds loud_seed,
+    loud_seed + 1, loud_seed + 2 for UNet, VAE, CLIP); the returned dicts are the ones the engine was built on."""
     from view_neti_amd import sd_config as sc, synth
     cfg = sc.CONFIGS[cfg_name]()
     dev = "cpu" if cfg_name.startswith("tiny") else "cuda"
     uw, vw, cw = synth.unet_weights(cfg.unet, device=dev), synth.vae_weights(cfg.vae, device=dev), synth.clip_weights(cfg.clip, device=dev)
+    if loud_seed is not None:
+        from helpers.loud_weights import loud
+        uw, vw, cw = loud(uw, loud_seed), loud(vw, loud_seed + 1), loud(cw, loud_seed + 2)
     sd, w_enc, extra = mapper_args(cfg_name, n_obj, with_view, perturb_seed, fork_rng, order)
     eng = TrainStepEngine(cfg, uw, vw, cw, B, H, W, sd, w_enc, 0.4, 0.2, **extra, **kw)
     return cfg, eng, (uw, vw, cw), sd, w_enc, extra

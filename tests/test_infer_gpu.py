@@ -32,6 +32,37 @@ def test_vae_decoder_tiny(B, h, w):
     assert 0.0 <= float(eng.image.min()) and float(eng.image.max()) <= 1.0
 
 
+@pytest.mark.parametrize("B,h,w", [(1, 8, 8), (2, 8, 16)])
+def test_vae_decoder_tiny_loud_weights_and_taps(B, h, w):
+    """test_vae_decoder_tiny on LOUD 1-D parameters (helpers/loud_weights.py), at the same bars, and every named tap of the
+    oracle — post_quant_conv, conv_in, the mid attention's GroupNorm, q/k/v projection and output, each ResNet's two
+    GroupNorm-SiLU outputs, h1 and out, the upsamplers, the head's norm — against the engine buffer that holds it.
+    Measured on an MI355X (fp16): raw 1.4e-3 (bar 5e-3); worst tap error per kind: attn.gn, attn.qkv, attn.out 4.7e-4 ..
+    5.0e-4 (bar 1e-3), conv, res.gn, res.h1, res.out, head.gn 1.1e-3 .. 1.4e-3 (bar 3e-3 = 2 x the worst, rounded up);
+    TAP["vae_dec"] in helpers/engine_taps.py lists each.  tests/test_engine_taps_cpu.py
+    proves that every dropped or mis-indexed 1-D tensor moves one of these quantities by twice its bar.  fp16 library only:
+    `t16` would widen bf16 bars eightfold, which leaves that proof no margin."""
+    from helpers import engine_taps as ET
+    from helpers.checks import DT
+    from view_neti_amd.engine.vae import VAEDecoderEngine
+    if DT != torch.float16:
+        pytest.skip("engine taps are measured and proven for the fp16 library")
+    cfg, wts, z = ET.vae_dec_case(B, h, w)
+    eng = VAEDecoderEngine(cfg, wts, B, h, w)
+    eng.z_in.copy_(z)
+    eng.forward()
+    torch.cuda.synchronize()
+    ref = ET.vae_dec_oracle(cfg, wts, z)
+    label = f"vae decoder loud {B}x{h}x{w}"
+    ref_img = (ref["end"] / 2 + 0.5).clamp(0, 1).permute(0, 2, 3, 1)
+    raw = eng.rgb[:, :3].float().cpu().view(B, 8 * h, 8 * w, 3)
+    e_raw = _rel(raw, ref["end"].permute(0, 2, 3, 1))
+    e_img = (eng.image.cpu() - ref_img).abs().max().item()
+    print(f"[{label}] raw rel {e_raw:.3e} (std {ref['end'].std():.3f}); image max abs {e_img:.3e}")
+    ET.compare(label, "vae_dec", {k: v for k, v in ref.items() if k != "end"}, ET.vae_buffers(eng), ET.norm_outputs(eng))
+    assert e_raw < ET.END["vae_dec"] and e_img < 2e-2
+
+
 @pytest.mark.parametrize("vpred", [False, True])
 def test_cfg_sampler_step_kernel(vpred):
     from view_neti_amd import ops

@@ -13,17 +13,39 @@ pytestmark = pytest.mark.gpu
 
 # config 2 (mode 0, SD-1.5 family) / config 3 (mode 2: object + view mappers) / SD-2.1 family switches
 # (linear projections, GELU CLIP, v-prediction; non-square DTU-like frame) / unconstrained bypass
-@pytest.mark.parametrize("cfg_name,with_view,H,W,unc", [("tiny", False, 64, 64, False), ("tiny", True, 64, 64, False),
-                                                        ("tiny21", True, 64, 128, False),
-                                                        ("tiny21", True, 64, 64, True)])
+TINY_STEPS = [("tiny", False, 64, 64, False), ("tiny", True, 64, 64, False), ("tiny21", True, 64, 128, False),
+              ("tiny21", True, 64, 64, True)]
+
+
+@pytest.mark.parametrize("cfg_name,with_view,H,W,unc", TINY_STEPS)
 def test_train_step_tiny_matches_oracle(cfg_name, with_view, H, W, unc):
+    _train_step_tiny(cfg_name, with_view, H, W, unc)
+
+
+@pytest.mark.parametrize("cfg_name,with_view,H,W,unc", TINY_STEPS)
+def test_train_step_tiny_loud_weights_and_taps(cfg_name, with_view, H, W, unc):
+    """test_train_step_tiny_matches_oracle with the 1-D parameters of the three frozen models made LOUD
+    (helpers/loud_weights.py), at the same bars, and every named tap of the oracle's VAE encoder, 16 CLIP passes and UNet
+    against the buffer of the step's own sub-engine that holds it, at the bars of the engine-level files
+    (helpers/engine_taps.py states the measured errors, which include these runs: the sub-engines' taps err by 3e-4 .. 1.5e-3
+    like the stand-alone engines'; loss 1.7e-5 .. 1.2e-4 relative, bar 1e-3).  fp16 library only: `t16` would widen bf16 bars eightfold, which
+    leaves the sharpness proof (tests/test_engine_taps_cpu.py) no margin; bf16 keeps its whole-step check."""
+    from helpers.checks import DT
+    if DT != torch.float16:
+        pytest.skip("engine taps are measured and proven for the fp16 library")
+    _train_step_tiny(cfg_name, with_view, H, W, unc, loud=True)
+
+
+def _train_step_tiny(cfg_name, with_view, H, W, unc, loud=False):
+    from helpers import engine_taps as ET
     from oracle import sd_ref as R
     from view_neti_amd import synth
     from view_neti_amd.engine.text import flatten_mapper_state
     B = 2
     lr = 4e-3
     cfg, eng, (uw, vw, cw), sd, w_enc, extra = build(cfg_name, B, H, W, with_view=with_view, device_rng=False, lr=lr,
-                                                     unconstrained_object=unc, unconstrained_view=unc)
+                                                     unconstrained_object=unc, unconstrained_view=unc,
+                                                     loud_seed=ET.LOUD_SEED if loud else None)
     ph = cfg.clip.vocab_size - 3
     phv = cfg.clip.vocab_size - 4
     ids = synth.input_ids(B, ph, cfg.clip.vocab_size, view_placeholder_id=phv if with_view else None)
@@ -47,8 +69,14 @@ def test_train_step_tiny_matches_oracle(cfg_name, with_view, H, W, unc):
         p_v = {k: v.clone().requires_grad_(True) for k, v in extra["mapper_view"].items()}
         view = dict(p=p_v, w_enc=extra["w_enc_view"], norm_scale=0.35, placeholder=torch.full((B,), phv),
                     params=vparams, alpha=0.3, unconstrained=unc)
+    taps = {} if loud else None
     loss, aux = R.train_step_loss(cfg, r16(uw), r16(vw), r16(cw), p_o, w_enc, 0.4, px, ids, torch.full((B,), ph), t,
-                                  eps, noise, alpha=0.2, unconstrained=unc, view=view)
+                                  eps, noise, alpha=0.2, unconstrained=unc, view=view, taps=taps)
+    if loud:
+        label = f"step loud {cfg_name} {H}x{W} view={with_view}"
+        ET.compare(label + " vae", "vae_enc", taps["vae"], ET.vae_buffers(eng.vae), ET.norm_outputs(eng.vae))
+        ET.compare(label + " text", "text", ET.stack_text_taps(taps["text"]), ET.text_buffers(eng.text), ET.norm_outputs(eng.text))
+        ET.compare(label + " unet", "unet", taps["unet"], ET.unet_buffers(eng.unet), ET.norm_outputs(eng.unet))
     loss.backward()
     ref = [flatten_mapper_state({k: v.grad for k, v in p_o.items()})]
     if with_view:

@@ -17,6 +17,27 @@ VARIANTS = [(False, False, False, False), (True, False, False, False), (False, T
 
 @pytest.mark.parametrize("with_view,unc_obj,unc_view,dropout", VARIANTS)
 def test_text_engine_tiny(with_view, unc_obj, unc_view, dropout):
+    _text_engine_tiny(with_view, unc_obj, unc_view, dropout)
+
+
+@pytest.mark.parametrize("with_view", [False, True])
+def test_text_engine_tiny_loud_weights_and_taps(with_view):
+    """test_text_engine_tiny (forward and backward, L = 77) on LOUD 1-D CLIP parameters (helpers/loud_weights.py), at the
+    same bars, and every named tap of the oracle's 16 CLIP passes — per layer the two LayerNorm outputs, the q/k/v
+    projection, the residual stream after the attention and after the MLP — against the engine buffer that holds it (rows
+    ordered pass, sample, token).  Measured on an MI355X (fp16): contexts 4.0e-4 (bar 5e-3); worst tap error per kind: ln
+    4.0e-4 (bar 9e-4), qkv 4.3e-4 (9e-4), attn 3.2e-4 (7e-4), mlp 3.6e-4 (8e-4): 2 x the worst, rounded up (TAP["text"] in
+    helpers/engine_taps.py).  tests/test_engine_taps_cpu.py proves that every dropped or mis-indexed 1-D tensor moves one of these quantities by twice
+    its bar.  fp16 library only: `t16` would widen bf16 bars eightfold, which leaves that proof no margin."""
+    from helpers.checks import DT
+    if DT != torch.float16:
+        pytest.skip("engine taps are measured and proven for the fp16 library")
+    _text_engine_tiny(with_view, False, False, False, loud=True)
+
+
+def _text_engine_tiny(with_view, unc_obj, unc_view, dropout, loud=False):
+    from helpers import engine_taps as ET
+    from helpers.loud_weights import loud as make_loud
     from oracle import sd_ref as R
     from view_neti_amd import sd_config as sc, synth
     from view_neti_amd.engine.text import MapperState, TextEngine, flatten_mapper_state
@@ -28,6 +49,8 @@ def test_text_engine_tiny(with_view, unc_obj, unc_view, dropout):
     # matmul operands are fp16 on the GPU: round those weights once for both sides
     wr = {k: (v.half().float() if (k.endswith("weight") and v.dim() == 2 and "embedding" not in k) else v)
           for k, v in w.items()}
+    if loud:
+        wr = make_loud(wr, ET.LOUD_SEED)
     ph_obj, ph_view = cfg.vocab_size - 3, cfg.vocab_size - 4
     ids = synth.input_ids(B, ph_obj, cfg.vocab_size, L, view_placeholder_id=ph_view if with_view else None)
     ids[1] = torch.roll(ids[1], 3)  # different placeholder positions per sample
@@ -91,8 +114,11 @@ def test_text_engine_tiny(with_view, unc_obj, unc_view, dropout):
         p_v = {k: v.clone().requires_grad_(True) for k, v in sdv.items()}
         view = dict(p=p_v, w_enc=w_enc_v, norm_scale=0.35, placeholder=torch.full((B,), ph_view), params=vparams,
                     alpha=0.3, unconstrained=unc_view, hidden_masks=masks_v)
+    taps = [] if loud else None
     hs = R.text_conditioning(wr, cfg, p_o, w_enc_o, 0.4, ids, torch.full((B,), ph_obj), t, alpha=0.2,
-                             unconstrained=unc_obj, n_layers=nl, view=view, hidden_masks=masks_o)
+                             unconstrained=unc_obj, n_layers=nl, view=view, hidden_masks=masks_o, taps=taps)
+    if loud:
+        ET.compare(f"text loud view={with_view}", "text", ET.stack_text_taps(taps), ET.text_buffers(eng), ET.norm_outputs(eng))
     rk = torch.stack([hs[f"CONTEXT_TENSOR_{i}"] for i in range(nl)]).reshape(nl, B * L, D)
     rv = torch.stack([hs[f"CONTEXT_TENSOR_BYPASS_{i}"] for i in range(nl)]).reshape(nl, B * L, D)
     ek, ev = _rel(ctx_k, rk.detach()), _rel(ctx_v, rv.detach())

@@ -64,3 +64,44 @@ def test_unet_tiny_fwd_bwd():
 
 def test_unet_tiny_nonsquare():
     _run("tiny", 1, 8, 16, 2e-2, 4e-2)
+
+
+@pytest.mark.parametrize("cfg_name,B,H,W", [("tiny", 2, 16, 16), ("tiny", 1, 8, 16), ("tiny21", 2, 16, 16), ("tiny21", 1, 8, 16)])
+def test_unet_loud_weights_and_taps(cfg_name, B, H, W):
+    """The same comparison on LOUD 1-D parameters (helpers/loud_weights.py: a dropped, swapped or mis-indexed bias, gain or
+    shift moves the result by many bars; tests/test_engine_taps_cpu.py proves it for every 1-D tensor), at the same
+    end-to-end bars, and every named tap of the oracle against the engine buffer that holds it (helpers/engine_taps.py,
+    which states the measured tap errors and their bars).  tiny21 runs the linear proj_in / proj_out form.  fp16 library
+    only: `t16` would widen bf16 bars eightfold, which leaves the sharpness proof no margin; bf16 keeps its whole-step check.
+    Measured on an MI355X (fp16): pred 1.2e-3 (bar 2e-2), worst context gradient 4.2e-3 (bar 4e-2); worst tap error per
+    kind, over these cases and the UNets of the loud whole steps: time 4.2e-4 (bar 9e-4), every other kind (conv, res.gn,
+    res.h1, res.out, tr.gn, tr.ln, tr.h0, tr.h1, tr.h2, tr.out, head.gn) 1.2e-3 .. 1.5e-3 (bar 3e-3 = 2 x the worst, rounded
+    up); TAP["unet"] in helpers/engine_taps.py lists each."""
+    from helpers import engine_taps as ET
+    from helpers.checks import DT
+    from view_neti_amd.engine.unet import UNetEngine
+    if DT != torch.float16:
+        pytest.skip("engine taps are measured and proven for the fp16 library")
+    cfg, w, inp = ET.unet_case(cfg_name, B, H, W)
+    eng = UNetEngine(cfg, w, B, H, W)
+    eng.x_in.copy_(inp["x"])
+    eng.timesteps.copy_(inp["t"])
+    eng.ctx_k.copy_(inp["ck"])
+    eng.ctx_v.copy_(inp["cv"])
+    eng.forward()
+    torch.cuda.synchronize()
+    ref, leaves = ET.unet_oracle(cfg, w, inp, grads=True)
+    label = f"unet loud {cfg_name} {B}x{H}x{W}"
+    pred = eng.pred.float().cpu().view(B, H, W, 4).permute(0, 3, 1, 2)
+    e = _rel(pred, ref["end"])
+    print(f"[{label}] pred rel err {e:.3e} (ref std {ref['end'].std().item():.3f})")
+    ET.compare(label, "unet", {k: v for k, v in ref.items() if k != "end"}, ET.unet_buffers(eng), ET.norm_outputs(eng))
+    assert math.isfinite(e) and e < ET.END["unet"]
+    eng.dpred.copy_(inp["dpred"].permute(0, 2, 3, 1).reshape(B * H * W, 4))
+    eng.backward()
+    torch.cuda.synchronize()
+    L, Dc = inp["L"], cfg.cross_attention_dim
+    worst = max(max(_rel(eng.dctx_k[i].view(B, L, Dc), a.grad), _rel(eng.dctx_v[i].view(B, L, Dc), b.grad))
+                for i, (a, b) in enumerate(leaves))
+    print(f"[{label}] worst context-gradient rel err {worst:.3e}")
+    assert math.isfinite(worst) and worst < ET.END["unet.grad"]
